@@ -2,17 +2,26 @@
 """bench.py -- orz -l1 encode throughput on MI355X (BASELINE.json metric).
 
 A "step" is one pass of the hot path over one batch: the full orz encode (`LZEncoder::encode`
-driven by `orz::encode`, /root/reference/src/lib.rs:58-92) of the 100,000,000-byte enwik8-shaped
+driven by `orz::encode`, the reference's src/lib.rs:58-92) of the 100,000,000-byte enwik8-shaped
 workload (tools/enwik_like.py: seeded, box-independent, SHA-256 pinned) at -l1, input already
 resident in HBM, one stream, one 16 MiB block in flight (BASELINE configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W [--mode fast|exact]
+  python bench.py --gpus N --steps K --warmup W [--mode fast|exact] [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; every rank encodes its own member
    -- a distinct rotation of the workload -- and the finished bitstreams are gathered to rank 0
    over RCCL; weak scaling.)
 
+A plain run sets up, runs W warm-up steps and K timed steps, and prints the headline line (the
+figures of the timed steps only).  --dump-outputs DIR then writes the stream of the last timed step
+(rank 0's) as DIR/compressed_sample.npy (float32 byte values at a fixed, seeded sample of 8 Mi
+positions, the whole stream when shorter), DIR/compressed_sha256.npy (the SHA-256 of the whole
+stream, 32 byte values, float32) and DIR/compressed_bytes.npy (its length, float64).
+--full adds what takes passes of its own, all outside the timed region: `roofline`,
+`roofline_others` and `kernel_table` (one profiled pass), the oracle round trip of the timed stream,
+`cpu_baseline` and, at N = 1, the members legs (--no-cpu-baseline / --no-members leave them out).
+
 Rank 0 prints ONE JSON line.  `config` is read back from the encoder (orz_stream_get_config), not
-written down here.  `roofline` describes the kernel with the largest share of device time, from HIP
+written down here.  With --full, `roofline` describes the kernel with the largest share of device time, from HIP
 events recorded inside the library on the stream each kernel runs on (orz_stream_get_kernel_times);
 `roofline_others` carries the next ones.  Algorithmic bytes per launch = 1.27 B per input byte
 (read the window once + write the bitstream, r ~= 0.27) x the input bytes one launch
@@ -298,7 +307,12 @@ def main():
     ap.add_argument("--members-bytes", type=int, default=16 << 26, help="bytes of the -l1 members leg (64 MiB members)")
     ap.add_argument("--mode", choices=["fast", "exact"], default="fast",
                     help="fast: GPU-native parse (reference-decodable, size within +-0.5 %%); exact: the reference's parse item for item")
+    ap.add_argument("--full", action="store_true",
+                    help="also the annexes: roofline and kernel table (a profiled pass), the oracle round trip, CPU baseline, members legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's stream (sample, SHA-256, length) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -384,15 +398,19 @@ def main():
     barrier()
     dt = time.time() - t0
     gather_ms = gather_s[0] / max(1, args.steps) * 1e3
-    # roofline leg, outside the timed region: one more pass in profile mode (HIP-event brackets around the kernels of
-    # the round loop, which the timed passes replay as a hipGraph), scaled to `steps` passes below
-    enc.set_profile(True)
-    step()
-    for i, (ms, n) in enumerate(enc.kernel_times()):
-        kt[i][0] = ms * args.steps
-        kt[i][1] = n * args.steps
-    ktable = enc.kernel_table()  # every kernel of the profiled pass by name
-    enc.set_profile(False)
+    # the last timed stream, taken before any further pass (at N > 1 the next pass would write the same buffer)
+    out_bytes = (out.cpu().numpy().tobytes() if isinstance(out, torch.Tensor) else bytes(out)) if rank == 0 else b""
+    ktable = []
+    if args.full:
+        # roofline leg, outside the timed region: one more pass in profile mode (HIP-event brackets around the kernels of
+        # the round loop, which the timed passes replay as a hipGraph), scaled to `steps` passes below
+        enc.set_profile(True)
+        step()
+        for i, (ms, n) in enumerate(enc.kernel_times()):
+            kt[i][0] = ms * args.steps
+            kt[i][1] = n * args.steps
+        ktable = enc.kernel_table()  # every kernel of the profiled pass by name
+        enc.set_profile(False)
     if distributed:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -409,54 +427,8 @@ def main():
     if rank == 0:
         total_bytes = len(data) * world * args.steps
         value = total_bytes / dt / 1e6
-        names = ["orz_wave_kernel<ParseWave>" if args.mode == "exact" else "orz_thread_kernel<FastEval>", "orz_symrank_kernel",
-                 "orz_wave_kernel<FastRowsWave>", "orz_wave_kernel<PathUpWave>"]
-        # HBM bytes per launch from the builder's PMC passes (NOT this run: rocprofv3 counters need their own passes), only if
-        # the file names the same kernel; labelled as such in `traffic_source`
-        pmc_file, pmc = newest_pmc_profile()
-
-        def roof(i):
-            ms, n = kt[i]
-            if not n or ms <= 0:
-                return None
-            avg_s = ms / 1e3 / n
-            bpl = ALGO_BYTES_PER_INPUT_BYTE * len(data) * args.steps / n
-            ach = bpl / avg_s / 1e9
-            tr = pmc.get(names[i])
-            return {"bound": "hbm", "kernel": names[i], "achieved": round(ach, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 8), "traffic": tr,
-                    "traffic_source": ("from_profile: " + pmc_file) if tr is not None else None,
-                    # measured HBM rate of this kernel: counter bytes per launch / average launch duration of THIS run
-                    "hbm_gbs": round(tr / avg_s / 1e9, 3) if tr is not None else None,
-                    "hbm_frac_of_peak": round(tr / avg_s / 1e9 / HBM_PEAK_GBS, 6) if tr is not None else None,
-                    "launches_per_step": n // args.steps,
-                    "avg_launch_us": round(avg_s * 1e6, 2), "algorithmic_bytes_per_launch": round(bpl, 1),
-                    "device_ms_per_step": round(ms / args.steps, 2)}
-
-        order = sorted(range(4), key=lambda i: -kt[i][0])
-        roofs = [r for r in (roof(i) for i in order) if r]
-        # ... and every other kernel of the profiled pass that takes a millisecond or more of a 16 MiB block (task 7):
-        # the same arithmetic from the per-name table (one profiled pass over the workload)
-        blocks = max(1.0, len(data) / float(1 << 24))
-        seen_k = {r["kernel"].split("<")[-1].rstrip(">") for r in roofs}
-        for name, ms, n in ktable:
-            kname = name.split("<")[0].split(" ")[0]
-            if not n or kname in seen_k or "symrank" in kname or ms / blocks < 1.0:
-                continue
-            avg_s = ms / 1e3 / n
-            bpl = ALGO_BYTES_PER_INPUT_BYTE * len(data) / n
-            tr = None
-            for k, v in (pmc or {}).items():
-                if k.endswith("<" + kname + ">"):
-                    tr = v
-            roofs.append({"bound": "hbm", "kernel": name, "achieved": round(bpl / avg_s / 1e9, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": round(bpl / avg_s / 1e9 / HBM_PEAK_GBS, 8), "traffic": tr,
-                          "traffic_source": ("from_profile: " + pmc_file) if tr is not None else None,
-                          "hbm_gbs": round(tr / avg_s / 1e9, 3) if tr is not None else None,
-                          "hbm_frac_of_peak": round(tr / avg_s / 1e9 / HBM_PEAK_GBS, 6) if tr is not None else None,
-                          "launches_per_step": n, "avg_launch_us": round(avg_s * 1e6, 2), "algorithmic_bytes_per_launch": round(bpl, 1),
-                          "device_ms_per_step": round(ms, 2)})
-        out_bytes = out.cpu().numpy().tobytes() if isinstance(out, torch.Tensor) else bytes(out)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out_bytes)
         res = {
             "metric": "orz -l1 encode throughput (enwik8-shaped text, 100 MB, one 16 MiB block in flight)",
             "value": round(value, 3),
@@ -493,11 +465,6 @@ def main():
             "host_syncs_per_block": round(agg["host_syncs"] / max(1, args.steps * -(-len(data) // (1 << 24))), 2),
             # (a stream of its own parses a block as units -- config.encoder.unit_bytes, orz_stream.h -- and the wait is the unit's)
             "host_syncs_per_unit": round(agg["host_syncs"] / max(1, args.steps * -(-len(data) // max(1, cfg.get("unit_bytes") or (1 << 24)))), 2),
-            "roofline": roofs[0] if roofs else None,
-            "roofline_others": roofs[1:],
-            # every kernel of one profiled pass over the workload (HIP events around each launch, on the stream it runs on; no graph
-            # replay in that pass), per 16 MiB block: launches, average launch, ms; HBM bytes per launch where the PMC file has them
-            "kernel_table": kernel_table_rows(ktable, len(data), pmc),
             # the whole pipeline against the same roofline: algorithmic bytes of a pass / wall time of a pass
             "pipeline": {"bound": "hbm", "achieved": round(ALGO_BYTES_PER_INPUT_BYTE * len(data) * world / (dt / args.steps) / 1e9, 4),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -513,40 +480,117 @@ def main():
                 "post": round(agg["t_post_s"] / args.steps, 4),
             },
         }
-        # parity of what was timed, outside the timed region: the last timed stream through the oracle's decoder, and its
-        # size against the oracle's encoder (the cpu_baseline leg encodes the same bytes)
-        ok, dec_s = oracle_check(data, out_bytes)
-        res["roundtrip_ok"] = bool(ok)
-        res["roundtrip_checker"] = "oracle decoder (oracle/orz_oracle.c), %.2f s" % dec_s
-        res["size_delta_pct"] = None
-        if not args.no_cpu_baseline:  # (rank 0, whatever N: the same one-thread oracle pass over the unrotated workload)
-            res["cpu_baseline"] = cpu_baseline(base, LEVEL)
-            ref = res["cpu_baseline"]["compressed_bytes"]
-            res["size_delta_pct"] = round(100.0 * (len(out_bytes) - ref) / ref, 4)
-        if world == 1 and not args.no_members:
-            enc.close()  # (the lone encoder's ~5 GB go back before the members' encoders are built)
-            try:
-                res.update(members_leg(base, LEVEL, jobs=args.members_jobs, total=args.members_bytes, device=local_rank))
-            except Exception as e:  # the headline line must not be lost to its annex
-                res["members"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            # BASELINE configs[2] / configs[4] at -l2 (src/main.rs:97-102: 45/27/18), a 64 MiB member per encoder each, every member
-            # through the oracle's decoder, size against the oracle on the same split, the many-core CPU baseline at -l2 beside it
-            nproc = (res.get("cpu_baseline_members") or {}).get("cores")
-            l2_total = min(args.members_bytes, args.members_jobs << 26)
-            for key, make in (("members_l2_text", lambda: base), ("members_l2_zeros", lambda: corpus.zeros_noise(l2_total))):
-                try:
-                    leg = members_leg(make(), 2, jobs=args.members_jobs, total=l2_total, device=local_rank, nproc=nproc)
-                    leg["members"]["cpu_baseline_members"] = leg["cpu_baseline_members"]
-                    leg["members"]["gpu_over_cpu_members"] = leg["gpu_over_cpu_members"]
-                    leg["members"]["workload"] = ("BASELINE configs[2]: enwik8-shaped text, -l2" if key.endswith("text") else
-                                                  "BASELINE configs[4]: zeros + 1 % noise, -l2") + ", %d bytes in 64 MiB members" % l2_total
-                    res[key] = leg["members"]
-                except Exception as e:
-                    res[key] = {"error": "%s: %s" % (type(e).__name__, e)}
+        if args.full:
+            full_annex(res, args, enc, kt, ktable, data, base, out_bytes, local_rank, world)
         print(json.dumps(res), flush=True)
     enc.close()
     if distributed:
         dist.destroy_process_group()
+
+
+def dump_outputs(dirname, stream):
+    """the stream the last timed step returned, as float32 / float64 arrays (at most 32 MiB in all): a fixed, seeded sample of
+    8 Mi of its bytes (all of them when it is shorter), the SHA-256 of the whole stream, and its length"""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    buf = np.frombuffer(stream, dtype=np.uint8)
+    sample = 8 << 20
+    if len(buf) > sample:
+        idx = np.sort(np.random.default_rng(0x6F727A).choice(len(buf), size=sample, replace=False))
+        buf = buf[idx]
+    np.save(os.path.join(dirname, "compressed_sample.npy"), buf.astype(np.float32))
+    np.save(os.path.join(dirname, "compressed_sha256.npy"), np.frombuffer(hashlib.sha256(stream).digest(), dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(dirname, "compressed_bytes.npy"), np.array([len(stream)], dtype=np.float64))
+
+
+def full_annex(res, args, enc, kt, ktable, data, base, out_bytes, local_rank, world):
+    """--full, rank 0, outside the timed region: roofline rows and kernel table of the profiled pass, the oracle round trip of
+    the last timed stream, the CPU baseline and the members legs"""
+    import corpus
+
+    names = ["orz_wave_kernel<ParseWave>" if args.mode == "exact" else "orz_thread_kernel<FastEval>", "orz_symrank_kernel",
+             "orz_wave_kernel<FastRowsWave>", "orz_wave_kernel<PathUpWave>"]
+    # HBM bytes per launch from the builder's PMC passes (NOT this run: rocprofv3 counters need their own passes), only if
+    # the file names the same kernel; labelled as such in `traffic_source`
+    pmc_file, pmc = newest_pmc_profile()
+
+    def roof(i):
+        ms, n = kt[i]
+        if not n or ms <= 0:
+            return None
+        avg_s = ms / 1e3 / n
+        bpl = ALGO_BYTES_PER_INPUT_BYTE * len(data) * args.steps / n
+        ach = bpl / avg_s / 1e9
+        tr = pmc.get(names[i])
+        return {"bound": "hbm", "kernel": names[i], "achieved": round(ach, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(ach / HBM_PEAK_GBS, 8), "traffic": tr,
+                "traffic_source": ("from_profile: " + pmc_file) if tr is not None else None,
+                # measured HBM rate of this kernel: counter bytes per launch / average launch duration of THIS run
+                "hbm_gbs": round(tr / avg_s / 1e9, 3) if tr is not None else None,
+                "hbm_frac_of_peak": round(tr / avg_s / 1e9 / HBM_PEAK_GBS, 6) if tr is not None else None,
+                "launches_per_step": n // args.steps,
+                "avg_launch_us": round(avg_s * 1e6, 2), "algorithmic_bytes_per_launch": round(bpl, 1),
+                "device_ms_per_step": round(ms / args.steps, 2)}
+
+    order = sorted(range(4), key=lambda i: -kt[i][0])
+    roofs = [r for r in (roof(i) for i in order) if r]
+    # ... and every other kernel of the profiled pass that takes a millisecond or more of a 16 MiB block (VERDICT round 4, task 7):
+    # the same arithmetic from the per-name table (one profiled pass over the workload)
+    blocks = max(1.0, len(data) / float(1 << 24))
+    seen_k = {r["kernel"].split("<")[-1].rstrip(">") for r in roofs}
+    for name, ms, n in ktable:
+        kname = name.split("<")[0].split(" ")[0]
+        if not n or kname in seen_k or "symrank" in kname or ms / blocks < 1.0:
+            continue
+        avg_s = ms / 1e3 / n
+        bpl = ALGO_BYTES_PER_INPUT_BYTE * len(data) / n
+        tr = None
+        for k, v in (pmc or {}).items():
+            if k.endswith("<" + kname + ">"):
+                tr = v
+        roofs.append({"bound": "hbm", "kernel": name, "achieved": round(bpl / avg_s / 1e9, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                      "frac": round(bpl / avg_s / 1e9 / HBM_PEAK_GBS, 8), "traffic": tr,
+                      "traffic_source": ("from_profile: " + pmc_file) if tr is not None else None,
+                      "hbm_gbs": round(tr / avg_s / 1e9, 3) if tr is not None else None,
+                      "hbm_frac_of_peak": round(tr / avg_s / 1e9 / HBM_PEAK_GBS, 6) if tr is not None else None,
+                      "launches_per_step": n, "avg_launch_us": round(avg_s * 1e6, 2), "algorithmic_bytes_per_launch": round(bpl, 1),
+                      "device_ms_per_step": round(ms, 2)})
+    res["roofline"] = roofs[0] if roofs else None
+    res["roofline_others"] = roofs[1:]
+    # every kernel of one profiled pass over the workload (HIP events around each launch, on the stream it runs on; no graph
+    # replay in that pass), per 16 MiB block: launches, average launch, ms; HBM bytes per launch where the PMC file has them
+    res["kernel_table"] = kernel_table_rows(ktable, len(data), pmc)
+    # parity of what was timed, outside the timed region: the last timed stream through the oracle's decoder, and its
+    # size against the oracle's encoder (the cpu_baseline leg encodes the same bytes)
+    ok, dec_s = oracle_check(data, out_bytes)
+    res["roundtrip_ok"] = bool(ok)
+    res["roundtrip_checker"] = "oracle decoder (oracle/orz_oracle.c), %.2f s" % dec_s
+    res["size_delta_pct"] = None
+    if not args.no_cpu_baseline:  # (rank 0, whatever N: the same one-thread oracle pass over the unrotated workload)
+        res["cpu_baseline"] = cpu_baseline(base, LEVEL)
+        ref = res["cpu_baseline"]["compressed_bytes"]
+        res["size_delta_pct"] = round(100.0 * (len(out_bytes) - ref) / ref, 4)
+    if world == 1 and not args.no_members:
+        enc.close()  # (the lone encoder's ~5 GB go back before the members' encoders are built)
+        try:
+            res.update(members_leg(base, LEVEL, jobs=args.members_jobs, total=args.members_bytes, device=local_rank))
+        except Exception as e:  # the headline line must not be lost to its annex
+            res["members"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        # BASELINE configs[2] / configs[4] at -l2 (src/main.rs:97-102: 45/27/18), a 64 MiB member per encoder each, every member
+        # through the oracle's decoder, size against the oracle on the same split, the many-core CPU baseline at -l2 beside it
+        nproc = (res.get("cpu_baseline_members") or {}).get("cores")
+        l2_total = min(args.members_bytes, args.members_jobs << 26)
+        for key, make in (("members_l2_text", lambda: base), ("members_l2_zeros", lambda: corpus.zeros_noise(l2_total))):
+            try:
+                leg = members_leg(make(), 2, jobs=args.members_jobs, total=l2_total, device=local_rank, nproc=nproc)
+                leg["members"]["cpu_baseline_members"] = leg["cpu_baseline_members"]
+                leg["members"]["gpu_over_cpu_members"] = leg["gpu_over_cpu_members"]
+                leg["members"]["workload"] = ("BASELINE configs[2]: enwik8-shaped text, -l2" if key.endswith("text") else
+                                              "BASELINE configs[4]: zeros + 1 % noise, -l2") + ", %d bytes in 64 MiB members" % l2_total
+                res[key] = leg["members"]
+            except Exception as e:
+                res[key] = {"error": "%s: %s" % (type(e).__name__, e)}
 
 
 if __name__ == "__main__":

@@ -12,10 +12,8 @@ README_SIZES = {2: 26_892_825, 1: 27_217_825, 0: 27_898_433}  # README.md:43,45,
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _enwik8(allow_reference_tree):
+def _enwik8():
     cands = [os.environ.get("ORZ_ENWIK8", ""), os.path.join(ROOT, "tests", "data", "enwik8"), os.path.join(ROOT, "tests", "data", "enwik8.xz")]
-    if allow_reference_tree:  # (the GPU box has no /root/reference: the gpu-marked test never looks there)
-        cands += ["/root/reference/test/enwik8", "/root/reference/test/enwik8.xz"]
     for p in cands:
         if p and os.path.exists(p):
             raw = open(p, "rb").read()
@@ -27,7 +25,7 @@ def _enwik8(allow_reference_tree):
 
 @pytest.mark.parametrize("level", [0, 1, 2])
 def test_oracle_reproduces_the_readme_sizes(oracle, level):
-    data = _enwik8(True)
+    data = _enwik8()
     out = oracle.encode(data, level)
     assert oracle.decode(out)[0] == data
     # the README's table was made with orz 1.6.2, this tree is 1.6.1: equality is expected, a few bytes would be a version note
@@ -39,7 +37,7 @@ def test_oracle_reproduces_the_readme_sizes(oracle, level):
 def test_gpu_modes_on_enwik8(oracle, level):
     import orz_amd
 
-    data = _enwik8(False)
+    data = _enwik8()
     exact = orz_amd.StreamEncoder(device=0, level=level, mode="exact")
     fast = orz_amd.StreamEncoder(device=0, level=level, mode="fast")
     try:

@@ -140,7 +140,7 @@ def test_bench_runs_under_torchrun_with_the_rccl_backend_at_world_size_one(tmp_p
     env = dict(os.environ, ORZ_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--bytes", "40000000",
-           "--no-members", "--no-cpu-baseline"]
+           "--full", "--no-members", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -141,7 +141,7 @@ def test_baseline_size_roundtrip_properties(gpu_encoder_factory, oracle):
     encoding is deterministic, and the size equals the oracle encoder's (well inside the +-0.5 % band)."""
     import corpus
 
-    data = corpus.text_corpus(100_000_000)
+    data = corpus.enwik_like(100_000_000)
     enc = gpu_encoder_factory(1)
     out = enc.encode(data)
     back, used = oracle.decode(out)
@@ -213,7 +213,7 @@ def test_baseline_configs_2_and_4_members_at_l2(oracle, kind):
 
     member = 1 << 24
     n = 2 * member + 3_000_000
-    data = corpus.text_corpus(100_000_000)[5_000_000:5_000_000 + n] if kind == "text" else corpus.zeros_noise(n)
+    data = corpus.enwik_like(100_000_000)[5_000_000:5_000_000 + n] if kind == "text" else corpus.zeros_noise(n)
     enc = orz_amd.MemberEncoder(device=0, level=2, jobs=2)
     try:
         container, nm = enc.encode(data, member_bytes=member)

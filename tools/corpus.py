@@ -89,7 +89,10 @@ def enwik_like(nbytes):
     if nbytes > full:  # larger inputs: whole copies + a prefix (the repeat distance is far beyond the 32 MiB window)
         base = enwik_like(full)
         return (base * (nbytes // full + 1))[:nbytes]
-    os.makedirs(CACHE, exist_ok=True)
+    try:
+        os.makedirs(CACHE, exist_ok=True)
+    except OSError:
+        pass
     path = os.path.join(CACHE, "E%d.bin" % full)
     data = None
     if os.path.exists(path) and os.path.getsize(path) == full:
@@ -98,14 +101,26 @@ def enwik_like(nbytes):
         if sha256(data) != _gen.MANIFEST[full]:
             data = None
     if data is None:
-        data = _gen.generate(full)
+        data = _gen.generate(full, jobs=_jobs())
         if sha256(data) != _gen.MANIFEST[full]:
             raise RuntimeError("enwik-like workload does not hash to the pinned value: %s" % sha256(data))
         tmp = "%s.%d.tmp" % (path, os.getpid())
-        with open(tmp, "wb") as f:
-            f.write(data)
-        os.replace(tmp, path)
+        try:  # (the cache only saves time: a cache directory this user cannot write is no error)
+            with open(tmp, "wb") as f:
+                f.write(data)
+            os.replace(tmp, path)
+        except OSError:
+            try:
+                os.remove(tmp)
+            except OSError:
+                pass
     return data[:nbytes]
+
+
+def _jobs():
+    """generator processes for the workload: the CPUs this process may use, at most 16"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    return max(1, min(16, n))
 
 
 def _splitmix64(first, n, seed):

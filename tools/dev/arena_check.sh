@@ -6,7 +6,7 @@ for a in 0 5632; do
   python tools/dev/members_scale.py 8 8 8 4 1 2>/dev/null | python3 -c "
 import json,sys
 print('ORZ_ARENA_MB=$a encoders 8 8 8 4 1 ->', [json.loads(l)['MBps'] for l in sys.stdin])"
-  python bench.py --no-cpu-baseline 2>/dev/null | python3 -c "
+  python bench.py --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read());print('ORZ_ARENA_MB=$a bench', d['value'], d['ms_per_step'], d['roundtrip_ok'])"
 done
 unset ORZ_ARENA_MB

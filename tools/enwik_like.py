@@ -13,6 +13,7 @@ standard sizes is pinned in MANIFEST below and checked by bench.py.
 import hashlib
 import os
 import re
+import subprocess
 import sys
 import zlib
 
@@ -178,9 +179,21 @@ def _chains(first, count, seed):
     return out
 
 
-def generate(nbytes, seed=0x656E77696B):
+def generate(nbytes, seed=0x656E77696B, jobs=1):
+    """jobs > 1: the chains are cut into `jobs` contiguous ranges, each generated by a fresh child process (a chain's bytes
+    depend only on its index and the seed, so the result is the same bytes)"""
     nch = (nbytes + CHAIN_BYTES - 1) // CHAIN_BYTES
     out = bytearray()
+    if jobs > 1 and nch >= 2 * jobs:
+        per = -(-nch // jobs)
+        procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "chains", str(first), str(min(per, nch - first)), str(seed)],
+                                  stdout=subprocess.PIPE) for first in range(0, nch, per)]
+        parts = [p.communicate()[0] for p in procs]  # (each child computes first and writes at the end: draining in order is enough)
+        if any(p.returncode != 0 for p in procs):
+            raise RuntimeError("a workload generator process failed")
+        for part in parts:
+            out += part
+        return bytes(out[:nbytes])
     for first in range(0, nch, 512):
         out += _chains(first, min(512, nch - first), seed)
     return bytes(out[:nbytes])
@@ -193,6 +206,9 @@ def sha256(data):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "train":
         train()
+    elif len(sys.argv) > 1 and sys.argv[1] == "chains":  # (one range of generate(..., jobs=N): raw bytes to stdout)
+        first, count, seed = (int(a) for a in sys.argv[2:5])
+        sys.stdout.buffer.write(_chains(first, count, seed))
     else:
         import bz2
         import time

@@ -26,7 +26,7 @@ IFS=';' read -ra SETS <<< "${VARIANTS:-}"
 for set in "${SETS[@]}"; do
   [ -z "$set" ] && continue
   ( IFS=','; for kv in $set; do export "$kv"; done
-    timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>>$OUT/${TAG}_variants.err | tail -1 | python -c "
+    timeout 300 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline 2>>$OUT/${TAG}_variants.err | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(json.dumps({'variant': '$set', 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'compressed_bytes': d['compressed_bytes'], 'roundtrip_ok': d['roundtrip_ok'], 'stage': d['stage_seconds_per_step']}))" ) | tee -a $OUT/${TAG}_variants.jsonl
 done
