@@ -219,6 +219,19 @@ int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t*
 size_t orz_huffman_stride(void);
 int orz_huffman_tables(int device, const uint32_t* weights, size_t nchunks, uint8_t* lens, uint16_t* codes, double* elapsed_us);
 
+/* Symbol ranking of one launch: 512 contexts' tables (value[389], index[389], cnt lo/hi, sum lo/hi as u16, the encoder's
+ * srstate layout, orz::kSrWords words a context) in and out; gsym[k] = symbol | excluded symbol << 16 in context order,
+ * rstart[513] the first item of each context.  Runs HipBackend::symrank (backup, kernel, SymCheck, guarded rerun).
+ * SymRankCoder::encode (src/symrank.rs:38-97) for every item of every context; `ranks` receives nitems ranks and `tables`
+ * the tables as the chains left them (contexts without items unchanged).  `flags2`, when not NULL, receives the guard's two
+ * counters (violations found after the first run, after the second; ORZ_SYMRANK_INJECT=k makes item k's first-run rank
+ * wrong, as in an encode).  `elapsed_us`, when not NULL, the HIP-event time of the whole sequence.  ORZ_EINVAL, before
+ * anything reaches the device, for rstart not monotone or not running from 0 to nitems, a symbol or excluded symbol of 389
+ * or more, value[] / index[] of a context that are not inverse permutations, a count above 390 or a sum above
+ * 1,151,320 (= 1,000,000 + 390 * 388, the largest the reference reaches). */
+int orz_symrank_chains(int device, uint16_t* tables, const uint32_t* gsym, const uint32_t* rstart, size_t nitems,
+                       uint16_t* ranks, uint32_t* flags2, double* elapsed_us);
+
 int orz_device_count(void);
 const char* orz_last_error(void);
 const char* orz_version(void);

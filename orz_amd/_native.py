@@ -173,6 +173,12 @@ SYMBOLS = [
         ctypes.c_int,
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)],
     ),
+    (
+        "orz_symrank_chains",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.POINTER(ctypes.c_double)],
+    ),
     ("orz_device_count", ctypes.c_int, []),
     ("orz_last_error", ctypes.c_char_p, []),
     ("orz_version", ctypes.c_char_p, []),

@@ -351,6 +351,58 @@ def huffman_tables(weights, device=0):
     return lens, codes, us.value
 
 
+SYMRANK_WORDS = 389 * 2 + 4  # a context's table in the encoder's layout: value[389], index[389], cnt lo/hi, sum lo/hi (u16)
+SYMRANK_MAX_SUM = 1000000 + 390 * 388  # the largest idx_sum the reference reaches (src/symrank.rs:22-29,63-66)
+
+
+def _symrank_inputs(tables, gsym, rstart):
+    """validated, contiguous copies of symrank_chains' arguments; ValueError for what the library would refuse"""
+    import numpy as np
+
+    t = np.asarray(tables)
+    if t.shape != (512, SYMRANK_WORDS) or not np.issubdtype(t.dtype, np.integer) or (t < 0).any() or (t > 0xFFFF).any():
+        raise ValueError("tables must be u16 values of shape [512, %d]" % SYMRANK_WORDS)
+    t = np.array(t, dtype=np.uint16, order="C", copy=True)  # (the library writes the final tables into it: never the caller's array)
+    g0 = np.asarray(gsym).reshape(-1)
+    if g0.size and (not np.issubdtype(g0.dtype, np.integer) or (g0 < 0).any() or (g0 >= (1 << 32)).any()):
+        raise ValueError("gsym must be integers symbol | excluded symbol << 16")
+    g = np.ascontiguousarray(g0, dtype=np.uint32)
+    if ((g & 0xFFFF) >= 389).any() or ((g >> 16) >= 389).any():
+        raise ValueError("symbols and excluded symbols must be below 389")
+    r0 = np.asarray(rstart).reshape(-1)
+    if r0.shape != (513,) or not np.issubdtype(r0.dtype, np.integer) or (r0 < 0).any():
+        raise ValueError("rstart must hold 513 non-negative integers")
+    r = np.ascontiguousarray(r0, dtype=np.int64)
+    if r[0] != 0 or r[512] != g.size or (np.diff(r) < 0).any():
+        raise ValueError("rstart must be monotone from 0 to len(gsym)")
+    val, idx = t[:, :389].astype(np.int64), t[:, 389:778].astype(np.int64)
+    if (val >= 389).any() or (np.take_along_axis(idx, val, axis=1) != np.arange(389)).any():
+        raise ValueError("value[] and index[] of every context must be inverse permutations")
+    cnt = t[:, 778].astype(np.int64) | (t[:, 779].astype(np.int64) << 16)
+    sm = t[:, 780].astype(np.int64) | (t[:, 781].astype(np.int64) << 16)
+    if (cnt > 390).any() or (sm > SYMRANK_MAX_SUM).any():
+        raise ValueError("count must be at most 390 and sum at most %d" % SYMRANK_MAX_SUM)
+    return t, g, r.astype(np.uint32)
+
+
+def symrank_chains(tables, gsym, rstart, device=0):
+    """The encoder's symbol-ranking sequence (HipBackend::symrank: backup, kernel, check, guarded rerun) ON THE GPU for one
+    launch -- SymRankCoder::encode (src/symrank.rs:38-97) over each context's items.  `tables`: [512, 782] u16 in the
+    encoder's layout; `gsym`: symbol | excluded symbol << 16 for every item, grouped by context; `rstart`: 513 offsets
+    -> (ranks uint16 array, tables as the chains left them, (flags[0], flags[1]) of the guard, microseconds of the sequence)."""
+    import numpy as np
+
+    t, g, r = _symrank_inputs(tables, gsym, rstart)
+    lib = _native.load()
+    ranks = np.zeros(g.size, dtype=np.uint16)
+    flags = np.zeros(2, dtype=np.uint32)
+    us = ctypes.c_double()
+    rc = lib.orz_symrank_chains(device, t.ctypes.data, g.ctypes.data, r.ctypes.data, g.size, ranks.ctypes.data, flags.ctypes.data,
+                                ctypes.byref(us))
+    _check(rc, "orz_symrank_chains")
+    return ranks, t, (int(flags[0]), int(flags[1])), us.value
+
+
 def decode_bytes(stream):
     """orz stream -> (bytes, consumed).  Host decoder of the library (orz::decode, src/lib.rs:94-129);
     stops after the first stream's EOF chunk like the reference."""

@@ -670,6 +670,54 @@ int orz_huffman_tables(int device, const uint32_t* weights, size_t nchunks, uint
     }
 }
 
+// ------------------------------------------------------------------------------ symbol ranking alone
+int orz_symrank_chains(int device, uint16_t* tables, const uint32_t* gsym, const uint32_t* rstart, size_t nitems,
+                       uint16_t* ranks, uint32_t* flags2, double* elapsed_us) {
+    if (!tables || !rstart || (!gsym && nitems) || (!ranks && nitems)) return fail(ORZ_EINVAL, "bad argument");
+    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    if (const char* why = orz::symrank_chains_invalid(tables, gsym, rstart, nitems)) return fail(ORZ_EINVAL, why);
+    try {
+        orz::HipBackend be(device);
+        const size_t nt = (size_t)512 * orz::kSrWords;
+        struct Bufs {
+            orz::HipBackend& be;
+            uint16_t *st = nullptr, *backup = nullptr, *rk = nullptr;
+            uint32_t *gs = nullptr, *rs = nullptr, *fl = nullptr;
+            ~Bufs() { be.free(st); be.free(backup); be.free(rk); be.free(gs); be.free(rs); be.free(fl); }
+        } b{be};
+        b.st = be.alloc<uint16_t>(nt, false);
+        b.backup = be.alloc<uint16_t>(nt, false);
+        b.rk = be.alloc<uint16_t>(nitems, false);
+        b.gs = be.alloc<uint32_t>(nitems, false);
+        b.rs = be.alloc<uint32_t>(513, false);
+        b.fl = be.alloc<uint32_t>(3);
+        be.h2d(b.st, tables, nt * 2);
+        be.h2d(b.gs, gsym, nitems * 4);
+        be.h2d(b.rs, rstart, 513 * 4);
+        struct Events {  // destroyed on every path out
+            hipEvent_t a = nullptr, b = nullptr;
+            ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+        } ev;
+        ORZ_HIP_CHECK(hipEventCreate(&ev.a));
+        ORZ_HIP_CHECK(hipEventCreate(&ev.b));
+        ORZ_HIP_CHECK(hipEventRecord(ev.a, be.stream()));
+        // the encoder's own sequence: backup, kernel, SymCheck, the guarded rerun (ORZ_SYMRANK_INJECT acts here as in an encode)
+        be.symrank(b.st, b.gs, b.rk, b.rs, (uint32_t)nitems, b.fl, b.backup, nullptr);
+        ORZ_HIP_CHECK(hipEventRecord(ev.b, be.stream()));
+        uint32_t fl[3] = {0, 0, 0};
+        be.d2h(fl, b.fl, sizeof fl);
+        be.d2h(tables, b.st, nt * 2);
+        if (nitems) be.d2h(ranks, b.rk, nitems * 2);
+        if (flags2) { flags2[0] = fl[0]; flags2[1] = fl[1]; }
+        float ms = 0;
+        ORZ_HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        if (elapsed_us) *elapsed_us = (double)ms * 1000.0;
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_EINVAL, e.what());
+    }
+}
+
 // ------------------------------------------------------------------------------ orz_lz_encoder
 orz_lz_encoder* orz_lz_encoder_new(int device) {
     try {

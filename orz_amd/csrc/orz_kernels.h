@@ -340,6 +340,29 @@ ORZ_HD void symrank_run(uint16_t* value, uint16_t* index, uint16_t* state, const
     state[2 * kSyms] = (uint16_t)cnt; state[2 * kSyms + 1] = (uint16_t)(cnt >> 16);
     state[2 * kSyms + 2] = (uint16_t)sum; state[2 * kSyms + 3] = (uint16_t)(sum >> 16);
 }
+// The largest idx_sum the reference reaches: 1,000,000 at the start plus 390 items of rank 388 (a count above 390 scales
+// first).  Above it `sum * 9` and the u16 quotient of src/symrank.rs:63-74 no longer mean what they mean in the reference.
+constexpr uint32_t kSrMaxSum = 1000000 + 390 * (kSyms - 1);
+// (host) what is wrong with one launch's input of the ranking chain (orz_symrank_chains, the emulation's twin), or nullptr:
+// 512 contexts' tables in the srstate layout, gsym[nitems], rstart[513].  Whatever the kernel indexes with is checked here.
+inline const char* symrank_chains_invalid(const uint16_t* tables, const uint32_t* gsym, const uint32_t* rstart, size_t nitems) {
+    if (nitems > (1u << 28)) return "more than 2^28 items";
+    if (rstart[0] != 0 || rstart[512] != nitems) return "rstart must run from 0 to nitems";
+    for (uint32_t c = 0; c < 512; c++)
+        if (rstart[c] > rstart[c + 1]) return "rstart is not monotone";
+    for (size_t k = 0; k < nitems; k++)
+        if ((gsym[k] & 0xffff) >= kSyms || (gsym[k] >> 16) >= kSyms) return "symbol or excluded symbol of 389 or more";
+    for (uint32_t c = 0; c < 512; c++) {
+        const uint16_t* t = tables + (size_t)c * kSrWords;
+        for (uint32_t i = 0; i < kSyms; i++)
+            if (t[i] >= kSyms || t[kSyms + t[i]] != i) return "value[] and index[] are not inverse permutations";
+        const uint32_t cnt = t[2 * kSyms] | ((uint32_t)t[2 * kSyms + 1] << 16);
+        const uint32_t sum = t[2 * kSyms + 2] | ((uint32_t)t[2 * kSyms + 3] << 16);
+        if (cnt > kSyms + 1) return "count above 390";
+        if (sum > kSrMaxSum) return "sum above 1,151,320";
+    }
+    return nullptr;
+}
 struct SymScatter {
     const uint32_t* perm;
     const uint16_t* grank;

@@ -389,7 +389,8 @@ __global__ __launch_bounds__(64) void orz_symrank_kernel(uint16_t* srstate, cons
         }
         cnt += 1;
         sum += i;
-        const uint32_t dec = (i >> 4) + (sum >> 4) / cnt, half = i >> 1;
+        // (u16 as in the reference: the quotient reaches 2^16 where a context starts with a small count and a large sum)
+        const uint32_t dec = ((i >> 4) + (((sum >> 4) / cnt) & 0xffff)) & 0xffff, half = i >> 1;
         uint32_t nx = i > dec ? i - dec : 0;
         nx = nx > half ? nx : half;
         const uint32_t y = (i + nx) >> 1;

@@ -433,6 +433,19 @@ extern "C" int emu_window_front(const uint8_t* src, size_t n, uint8_t* front2) {
     }
 }
 extern "C" void emu_free(void* p) { std::free(p); }
+// orz_symrank_chains on the emulation backend: the same validation, the backend's symrank (the plain loop of orz_kernels.h)
+extern "C" int emu_symrank(int, uint16_t* tables, const uint32_t* gsym, const uint32_t* rstart, size_t nitems, uint16_t* ranks,
+                           uint32_t* flags2, double* elapsed_us) {
+    if (!tables || !rstart || (!gsym && nitems) || (!ranks && nitems)) { g_emu_err = "bad argument"; return -1; }
+    if (const char* why = orz::symrank_chains_invalid(tables, gsym, rstart, nitems)) { g_emu_err = why; return -1; }
+    EmuBackend be;
+    uint32_t flags[3];
+    const auto t0 = std::chrono::steady_clock::now();
+    be.symrank(tables, gsym, ranks, rstart, (uint32_t)nitems, flags, nullptr, nullptr);
+    if (elapsed_us) *elapsed_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (flags2) { flags2[0] = flags[0]; flags2[1] = flags[1]; }
+    return 0;
+}
 // the Huffman table kernel alone (orz_kernels.h, HuffWave): nchunks x kHwStride weights in, lengths and codes out
 extern "C" int emu_huff_build(const uint32_t* hw, unsigned nchunks, uint8_t* hl, uint16_t* hc) {
     EmuBackend be;
