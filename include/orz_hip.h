@@ -209,6 +209,22 @@ typedef struct {
 } orz_decode_stats;
 int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len,
                               size_t* n_members_out, orz_decode_stats* stats);
+/* Members decoded from and into DEVICE memory.  `src` holds n bytes (device memory of `device` when src_on_device != 0, host
+ * memory otherwise).  Layout: offs == NULL -> src is one concatenation of members (what orz_members_encode / orz_stream_encode
+ * write); offs != NULL -> member k is the lens[k] bytes at src + offs[k] (host arrays of n_members entries, any order and gaps
+ * allowed: what orz_members_encode_to_device reports; offs and lens are both given or both NULL).  Output: the members' bytes
+ * concatenated in member order at d_dst (d_cap bytes on `device`); *dst_len = total decoded size, *n_members_out = members,
+ * out_offs (optional host array, one entry a member) = where each member's bytes start.  d_dst == NULL with d_cap == 0 only
+ * sizes: fills *dst_len / *n_members_out / out_offs and decodes nothing.  ORZ_ENOMEM when d_cap < *dst_len (nothing written to
+ * d_dst; *dst_len and *n_members_out are filled); ORZ_EINVAL for malformed data, for a table entry out of range or not ending at
+ * its member's EOF byte, and for a device-resident src that overlaps the d_cap bytes at d_dst -- the message names the first bad
+ * member.  The framing is indexed ON the device (orz_decode_index.h): no host copy of the container or the output is made.
+ * Bytes identical to orz_decode_members_mem; returns after the last byte is written.  Nothing outside
+ * [d_dst, d_dst + *dst_len) is written, and the output does not depend on what d_dst held.  ORZ_DECODE_SLOTS = members in
+ * flight, as for orz_decode_members_device. */
+int orz_decode_members_to_device(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                                 size_t n_members, uint8_t* d_dst, size_t d_cap, size_t* dst_len, size_t* n_members_out,
+                                 size_t* out_offs, orz_decode_stats* stats);
 
 /* The Huffman tables of `nchunks` chunks on the device, in the layout the encoder keeps them: a chunk is
  * orz_huffman_stride() = 389 + 389 + 240 entries (symbol ranks after a match / after a literal, long match lengths:

@@ -328,6 +328,63 @@ def decode_members_device(container, device=0, stats=False):
     return (out, nm.value, st.as_dict()) if stats else (out, nm.value)
 
 
+def decode_members_to_device(src, device=0, members=None, out=None, offsets=False, stats=False):
+    """decode members ON THE GPU from device (or host) memory into device memory (orz_decode_members_to_device): the framing is
+    indexed on the GPU, nothing passes through the host.  `src`: a uint8 torch tensor on cuda:`device` or on the CPU, or
+    bytes-like.  `members`: None = `src` is one concatenation of members; else [(offset, length)] per member in member order, in
+    any order and with gaps in `src` (what MemberEncoder.encode_to_device returns).  `out`: a uint8 tensor on the device to
+    decode into (its first dst_len bytes are written, nothing else); by default one of the exact size is allocated.  Returns
+    (tensor of dst_len bytes on the device, n_members[, offsets: where each member's bytes start][, stats dict])."""
+    import torch
+
+    lib = _native.load()
+    dev = torch.device("cuda", int(device))
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError("src must be a contiguous uint8 tensor")
+        if src.is_cuda and src.device != dev:
+            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
+        keep, on_dev = src, src.is_cuda
+        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
+    else:
+        data = bytes(src)
+        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    if out is not None and (out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
+    if members is None:
+        offs = lens = None
+        nt = 0
+    else:
+        nt = len(members)
+        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
+        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
+    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+    dlen, nm = ctypes.c_size_t(), ctypes.c_size_t()
+
+    def call(dst, cap, oo, st):
+        rc = lib.orz_decode_members_to_device(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dst, cap, ctypes.byref(dlen),
+                                              ctypes.byref(nm), oo, ctypes.byref(st) if st is not None else None)
+        _check(rc, "orz_decode_members_to_device")
+
+    if out is None or (offsets and members is None):
+        call(None, 0, None, None)  # the sizing call: total size and member count
+    if out is None:
+        out = torch.empty(dlen.value, dtype=torch.uint8, device=dev)
+    # (an empty output still gets a real buffer of capacity 0: members that are all empty are decoded, and so checked)
+    dst = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=dev)
+    oo = (ctypes.c_size_t * max(nm.value if members is None else nt, 1))() if offsets else None
+    st = _native.DecodeStats()
+    call(ctypes.c_void_p(dst.data_ptr()), out.numel(), oo, st)
+    del keep
+    res = [out[: dlen.value], nm.value]
+    if offsets:
+        res.append([oo[k] for k in range(nm.value)])
+    if stats:
+        res.append(st.as_dict())
+    return tuple(res)
+
+
 def huffman_tables(weights, device=0):
     """Huffman code lengths and canonical codes of every table of `weights` ON THE GPU -- an array of shape
     [nchunks, orz_huffman_stride()] of symbol weights below 2^23 in the encoder's layout (389 + 389 + 240 symbols a chunk;

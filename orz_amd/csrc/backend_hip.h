@@ -452,12 +452,31 @@ class HipBackend {
         hipLaunchKernelGGL(orz_thread_kernel<F>, dim3(grid), dim3(256), 0, stream_, f, n);
         ORZ_HIP_CHECK(hipGetLastError());
     }
+    // hipFuncSetAttribute acts on the device current at the call: the LDS limit is raised once per (kernel, device), with this
+    // backend's device current, and the outcome is remembered per device (a lock-free check on every launch after the first;
+    // two threads that race on the first launch both make the same, idempotent call)
+    template <auto Kernel>
+    hipError_t big_lds(int bytes) {
+        static std::atomic<int> done[64];  // per device ordinal: 0 = not asked yet, else 1 + the outcome
+        std::atomic<int>* d = device_ >= 0 && device_ < 64 ? &done[device_] : nullptr;
+        if (d) {
+            const int v = d->load(std::memory_order_acquire);
+            if (v) return (hipError_t)(v - 1);
+        }
+        int cur = -1;
+        ORZ_HIP_CHECK(hipGetDevice(&cur));
+        if (cur != device_) ORZ_HIP_CHECK(hipSetDevice(device_));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (cur != device_) ORZ_HIP_CHECK(hipSetDevice(cur));
+        if (d) d->store(1 + (int)e, std::memory_order_release);
+        return e;
+    }
     template <class K>
     void launch_waves(size_t nblocks, const K& k, size_t lds_bytes) {
         if (!nblocks) return;
         Bracket br(*this, profile_ ? KernelNames::of<K>() : 0);
-        if (lds_bytes > 64 * 1024) {  // more than 64 KB of dynamic LDS (a CU of gfx950 has 160 KB) has to be asked for once per kernel
-            static const hipError_t big = hipFuncSetAttribute(reinterpret_cast<const void*>(&orz_wave_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+        if (lds_bytes > 64 * 1024) {  // more than 64 KB of dynamic LDS (a CU of gfx950 has 160 KB) has to be asked for
+            const hipError_t big = big_lds<&orz_wave_kernel<K>>(160 * 1024 - 256);
             if (big != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(big));
         }
         hipLaunchKernelGGL(orz_wave_kernel<K>, dim3((unsigned)nblocks), dim3(64), lds_bytes, stream_, k);
@@ -467,9 +486,8 @@ class HipBackend {
     void launch_group(const K& k) {
         Bracket br(*this, profile_ ? KernelNames::of<K>() : 0);
         size_t lds = k.lds_bytes();
-        // more than 64 KB of dynamic LDS (a CU of gfx950 has 160 KB) has to be asked for once per kernel
-        static const bool big_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&orz_group_kernel<K>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)K::kLdsMax) == hipSuccess;
+        // more than 64 KB of dynamic LDS (a CU of gfx950 has 160 KB) has to be asked for
+        const bool big_ok = big_lds<&orz_group_kernel<K>>((int)K::kLdsMax) == hipSuccess;
         if (lds > 64 * 1024 && !big_ok) lds = 0;  // (the kernel then works on global memory)
         hipLaunchKernelGGL(orz_group_kernel<K>, dim3(1), dim3(1024), lds, stream_, k, lds != 0);
         ORZ_HIP_CHECK(hipGetLastError());

@@ -16,6 +16,7 @@
 #include "../../include/orz_hip.h"
 #include "backend_hip.h"
 #include "orz_decode_device.h"
+#include "orz_decode_index.h"
 #include "orz_host_decode.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
@@ -623,6 +624,38 @@ int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t*
             stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
         }
         return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_EINVAL, e.what());
+    }
+}
+
+int orz_decode_members_to_device(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                                 size_t n_members, uint8_t* d_dst, size_t d_cap, size_t* dst_len, size_t* n_members_out,
+                                 size_t* out_offs, orz_decode_stats* stats) {
+    if ((!src && n) || !dst_len || (!d_dst && d_cap) || (!offs != !lens))
+        return fail(ORZ_EINVAL, "bad argument");
+    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "the member table is handed to the device as 64-bit words");
+    uint64_t total = 0, members = 0;
+    try {
+        orz::HipBackend be(device);
+        orz::DecodeToDeviceStats st;
+        orz::decode_members_to_device(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
+                                      (const uint64_t*)lens, n_members, d_dst, d_cap, total, members, (uint64_t*)out_offs, st,
+                                      env_u("ORZ_DECODE_SLOTS", 2048));
+        *dst_len = (size_t)total;
+        if (n_members_out) *n_members_out = (size_t)members;
+        if (stats) {
+            stats->members = st.members; stats->in_bytes = st.in_bytes; stats->out_bytes = st.out_bytes;
+            stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
+        }
+        return ORZ_OK;
+    } catch (const orz::DecodeCapacityError& e) {  // (the size is known: reported as the sizing call reports it)
+        *dst_len = (size_t)total;
+        if (n_members_out) *n_members_out = (size_t)members;
+        return fail(ORZ_ENOMEM, e.what());
+    } catch (const std::bad_alloc& e) {
+        return fail(ORZ_ENOMEM, e.what());
     } catch (const std::exception& e) {
         return fail(ORZ_EINVAL, e.what());
     }
