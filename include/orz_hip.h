@@ -168,6 +168,18 @@ int orz_stream_set_item_trace(orz_stream*, int on);
 /* copies up to cap items to out, returns the total number traced (or a negative error) */
 long orz_stream_get_item_trace(orz_stream*, orz_item* out, size_t cap);
 
+/* FOR TESTS: the static tables of one block of the fast parse (orz_fast.h, FastArgs), read between the block's prep kernels and
+ * its first round.  name == NULL arms the capture for the `arm_block`-th encode_block call (0 = the first; a block encoded in
+ * units makes one call per unit) of the NEXT encode on this stream, arm_block < 0 disarms; returns 0.  An armed encode waits
+ * for the prep kernels of that block and copies its tables to host memory; its stream is the one an unarmed encode writes, and
+ * an unarmed encode does nothing for this.  With a name: the size in bytes of that table of the captured block, of which up to
+ * `cap` bytes are copied to dst.  Names: "scalars" (eight u64: n, nhist, nent, nk, K, stream offset of the block's first new
+ * byte, block number, window offset of that byte), "hpos", "wsnap", "epos", "keys", "idx" (of the n new positions), "runstart",
+ * "rlen", "vbits", "stext", "cl", "ccnt", "rows" (n x K), "rdist", "kpos", "kkeys", "krun", "kw", "wmask", "kmeta", "hcm",
+ * "hpre".  ORZ_EINVAL, before anything reaches the device: an exact-mode stream, a block number above 65535, a name that no
+ * table has, no captured block. */
+long orz_stream_fast_tables(orz_stream*, int arm_block, const char* name, void* dst, size_t cap);
+
 /* ---- many members per GPU (independent chunks, each a complete orz stream) ------------
  * A stream does not shard (its model state is one adaptive chain), so throughput beyond one stream
  * comes from encoding independent members concurrently: `jobs` stream encoders on one device, each fed

@@ -174,6 +174,35 @@ class StreamEncoder:
                        ("src", "<u4")])
         return np.frombuffer(buf, dtype=dt, count=n).copy()
 
+    # the tables orz_stream_fast_tables hands out, and what they hold
+    FAST_TABLES = {"hpos": "<u4", "wsnap": "u1", "epos": "<u4", "keys": "<u4", "idx": "<u4", "runstart": "<u4", "rlen": "u1", "vbits": "<u8",
+                   "stext": "<u8", "cl": "<u8", "ccnt": "<u4", "rows": "u1", "rdist": "<u8", "kpos": "<u4", "kkeys": "<u4", "krun": "<u4",
+                   "kw": "<u2", "wmask": "<u8", "kmeta": "<u2", "hcm": "<u4", "hpre": "<u4"}
+
+    def arm_fast_tables(self, block):
+        """FOR TESTS: the next encode() keeps the static tables of its `block`-th encode_block call (None: disarm)."""
+        rc = self._lib.orz_stream_fast_tables(self._h, -1 if block is None else int(block), None, None, 0)
+        if rc < 0:
+            _check(rc, "orz_stream_fast_tables")
+
+    def fast_tables(self):
+        """FOR TESTS: the tables of the captured block: {name: numpy array} plus the scalars n, nhist, nent, nk, K, stream_off."""
+        import numpy as np
+
+        def get(name, dtype):
+            size = self._lib.orz_stream_fast_tables(self._h, 0, name.encode(), None, 0)
+            if size < 0:
+                _check(size, "orz_stream_fast_tables")
+            buf = np.empty(size, dtype=np.uint8)
+            self._lib.orz_stream_fast_tables(self._h, 0, name.encode(), buf.ctypes.data, size)
+            return buf.view(dtype)
+
+        sc = get("scalars", "<u8")
+        out = {k: int(sc[i]) for i, k in enumerate(("n", "nhist", "nent", "nk", "K", "stream_off", "block", "new_at"))}
+        for name, dtype in self.FAST_TABLES.items():
+            out[name] = get(name, dtype)
+        return out
+
     def close(self):
         if self._h:
             self._lib.orz_stream_free(self._h)

@@ -100,6 +100,7 @@ struct orz_stream {
     unsigned seg, win;
     orz::ItemTrace trace;
     bool tracing = false;
+    orz::FastTableCapture tables;  // (tests) orz_stream_fast_tables
     bool fast = false;
     unsigned ftile = orz::kFastTile, frounds = orz::kFastRounds;
     unsigned unit = 0;  // fast mode: bytes per unit of a block; 0 = the encoder's default (a stream that has the GPU to itself)
@@ -127,6 +128,7 @@ struct orz_stream {
         be->clear_graphs();  // (captured launches hold the old encoder's buffer addresses)
         enc = std::move(fresh);
         enc->trace = tracing ? &trace : nullptr;
+        enc->tables = &tables;
     }
     // apply a settings change + rebuild as a transaction: on failure every setting is as before and the old encoder lives on
     template <class Change>
@@ -300,6 +302,10 @@ static orz::StreamEncoder<orz::HipBackend>::DeviceResult stream_encode_device(or
     } else {
         (void)hipGetLastError();  // (registration refused: pageable copies, synchronised per block)
     }
+    struct Disarm {  // (tests) a capture is armed for ONE encode, whether it reached the block or not
+        orz::FastTableCapture& c;
+        ~Disarm() { c.arm = -1; }
+    } disarm{s->tables};
     const auto r = orz::encode_stream_device(*s->enc, be, (const uint8_t*)src, n, src_on_device != 0, d_dst, d_cap, pinned);
     if (stats) {
         float total = 0;
@@ -381,6 +387,25 @@ long orz_stream_get_item_trace(orz_stream* s, orz_item* out, size_t cap) {
         out[i] = it;
     }
     return (long)n;
+}
+
+// (tests) the static tables of one block of the fast parse, see include/orz_hip.h
+long orz_stream_fast_tables(orz_stream* s, int arm_block, const char* name, void* dst, size_t cap) {
+    if (!s || !s->enc) return fail(ORZ_EINVAL, "null stream");
+    if (!s->enc->fast()) return fail(ORZ_EINVAL, "the exact mode has no such tables");
+    orz::FastTableCapture& c = s->tables;
+    if (!name) {
+        if (arm_block > 65535) return fail(ORZ_EINVAL, "bad block number");
+        c.arm = arm_block < 0 ? -1 : arm_block;
+        c.taken = false;
+        c.tab.clear();
+        return 0;
+    }
+    if (!c.taken) return fail(ORZ_EINVAL, "no block was captured");
+    const std::vector<uint8_t>* t = c.find(name);
+    if (!t) return fail(ORZ_EINVAL, "no such table");
+    if (dst && cap) std::memcpy(dst, t->data(), std::min(cap, t->size()));
+    return (long)t->size();
 }
 
 // ------------------------------------------------------------------------------ members

@@ -38,6 +38,19 @@ struct ItemTrace {
     void clear() { block.clear(); pos.clear(); src.clear(); sym.clear(); ctx.clear(); rank.clear(); rob.clear(); unl.clear(); enc.clear(); al.clear(); mlen.clear(); }
 };
 
+// (tests) the static tables of ONE block of the fast parse as its rounds find them, copied to host memory between the prep kernels
+// and the first round (StreamEncoder::fast_parse).  `arm` = which encode_block call of the next stream is captured (-1 = none: the
+// encoder then does nothing for this -- no launch, no copy, no wait).  tests/_fasttables.py holds every table to its definition.
+struct FastTableCapture {
+    int arm = -1;
+    bool taken = false;
+    std::vector<std::pair<std::string, std::vector<uint8_t>>> tab;  // name -> bytes, in the order taken
+    const std::vector<uint8_t>* find(const char* name) const {
+        for (const auto& t : tab) if (t.first == name) return &t.second;
+        return nullptr;
+    }
+};
+
 struct EncodeStats {
     uint64_t blocks = 0, sweeps = 0, seg_evals = 0, items = 0, chunks = 0, in_bytes = 0, out_bytes = 0;
     uint64_t rank_redos = 0;  // blocks whose symbol ranking was repeated by the guard (backend symrank)
@@ -874,6 +887,43 @@ class StreamEncoder {
         fclose(f);
     }
 
+    // (tests) the block's static tables -> *tables, restricted to what the block uses; waits for the prep kernels (a test hook)
+    void capture_tables(uint32_t n, uint32_t nent, const uint32_t* slot_keys, const uint32_t* word_keys) {
+        FastTableCapture& c = *tables;
+        const uint32_t nhist = nent - n, nk = n + 1;
+        c.tab.clear();
+        be_.sync();
+        auto put = [&](const char* name, const void* dev, size_t bytes) {
+            c.tab.emplace_back(name, std::vector<uint8_t>(bytes));
+            be_.d2h(c.tab.back().second.data(), dev, bytes);
+        };
+        const uint64_t sc[8] = {n, nhist, nent, nk, fK_, stats.in_bytes, stats.blocks, kPre};
+        c.tab.emplace_back("scalars", std::vector<uint8_t>((const uint8_t*)sc, (const uint8_t*)sc + sizeof sc));
+        put("hpos", hpos_, (size_t)nhist * 4);
+        put("wsnap", wsnap_, 65536);
+        put("epos", epos_, (size_t)nent * 4);
+        put("keys", slot_keys, (size_t)nent * 4);
+        put("idx", idx_ + kPre, (size_t)n * 4);
+        put("runstart", runstart_, (size_t)kNumKeys * 4);
+        put("rlen", frlen_, n);
+        put("vbits", vbits_, ((size_t)nent / 64 + 2) * 8);
+        put("stext", fstext_, (size_t)nent * 16);
+        put("cl", fcl_, (size_t)nent * 16);
+        put("ccnt", fccnt_, (size_t)kNumKeys * 4);
+        put("rows", frows_, (size_t)n * fK_);
+        put("rdist", frdist_, (size_t)n * 8);
+        put("kpos", kpos_, (size_t)nk * 4);
+        put("kkeys", word_keys, (size_t)nk * 4);
+        put("krun", krun_, 32768 * 4);
+        put("kw", fkw_, (size_t)nk * 2);
+        put("wmask", fwmask_, (size_t)n * 8);
+        put("kmeta", fkmeta_, (size_t)n * 2);
+        put("hcm", fhcm_, (size_t)kHistSub * 256 * 4);
+        put("hpre", fhpre_, (size_t)(kHistSub + 1) * 256 * 4);
+        c.taken = true;
+        c.arm = -1;
+    }
+
     // The GPU-native parse of one block (orz_fast.h): fills S_/TY_/ML_/SRC_/ORD_/W0_ for the new region and
     // carries ctxcount_ / wsnap_ / lt_carry_, like the exact mode's sweeps + FinalizeBlock do.
     template <class OutT>
@@ -894,6 +944,7 @@ class StreamEncoder {
         be_.timed_begin(2);
         be_.launch_waves(((size_t)nent + 63) / 64, FastRowsWave{win, epos_, stext, frlen_, nent, K, frows_, frdist_}, FastRowsWave::lds_bytes(K));
         be_.timed_end(2);
+        if (tables && tables->arm >= 0 && (uint64_t)tables->arm == stats.blocks) capture_tables(n, nent, slot_keys, word_keys);
         FastArgs a;
         a.win = win; a.len = len; a.n = n; a.K = K; a.depth = (uint32_t)cfg_.depth; a.lazy1 = (uint32_t)cfg_.lazy1;
         a.lazy2 = (uint32_t)cfg_.lazy2; a.tile = ftile_; a.dmax = dmax_; a.nent = nent; a.nk = nk;
@@ -1660,6 +1711,7 @@ class StreamEncoder {
 
     EncodeStats stats;
     ItemTrace* trace = nullptr;  // when set, every block appends its items
+    FastTableCapture* tables = nullptr;  // (tests) when set and armed, one block's static tables are copied out (fast_parse)
 
    private:
     // device allocation owned by this encoder (freed by release_all, also when the constructor throws); `zero` = false for

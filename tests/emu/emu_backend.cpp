@@ -55,6 +55,9 @@ struct EmuBackend {
     }
     ~EmuBackend() { std::free(arena); }
     long fail_alloc_in = -1;  // (tests) the allocation that many calls from now throws std::bad_alloc; -1 = never
+    const bool* stop_when = nullptr;  // (tests) once *stop_when is set the next launch ends the encode (emu_fast_tables: the tables are taken)
+    struct Stop {};
+    void maybe_stop() const { if (stop_when && *stop_when) throw Stop{}; }
     template <class T> T* alloc(size_t n, bool zero = true) {
         if (fail_alloc_in == 0) { fail_alloc_in = -1; throw std::bad_alloc(); }
         if (fail_alloc_in > 0) fail_alloc_in--;
@@ -159,6 +162,7 @@ struct EmuBackend {
         pool.run(body);
     }
     template <class F> void launch(size_t n, const F& f) {
+        maybe_stop();
         const size_t nw = (n + 63) / 64;
         if (nw < 2) { for (size_t i = 0; i < n; i++) f(i); return; }
         on_threads([&](unsigned t) {
@@ -179,6 +183,7 @@ struct EmuBackend {
     }
 #else
     template <class F> void launch(size_t n, const F& f) {
+        maybe_stop();
         for (size_t i = 0; i < n; i++) f(i);
     }
     template <class K> void launch_waves(size_t nblocks, const K& k, size_t lds_bytes) {
@@ -414,6 +419,54 @@ extern "C" long emu_encode_fast_trace(const uint8_t* src, size_t n, int depth, i
     } catch (const std::exception& e) {
         std::fprintf(stderr, "emu_encode_fast_trace: %s\n", e.what());
         return -1;
+    }
+}
+// orz_stream_fast_tables on the emulation backend: `src` is encoded up to its `block`-th encode_block call, whose static tables
+// are kept (the encode ends there); the items of the units before it go to `items` (returns their number, -1 on failure, -2
+// when the stream has no such block).  emu_fast_table then copies a table of that capture by name, like the library's entry.
+static orz::FastTableCapture g_emu_tables;
+extern "C" long emu_fast_tables(const uint8_t* src, size_t n, int depth, int lazy1, int lazy2, int block, EmuItem* items, size_t cap) {
+    try {
+        EmuBackend be;
+        orz::Cfg cfg{depth, lazy1, lazy2};
+        orz::StreamEncoder<EmuBackend> enc(be, cfg, 62, 64, true, orz::kFastTile, orz::kFastRounds);
+        orz::ItemTrace tr;
+        enc.trace = &tr;
+        g_emu_tables = orz::FastTableCapture();
+        g_emu_tables.arm = block;
+        be.stop_when = &g_emu_tables.taken;
+        enc.tables = &g_emu_tables;
+        std::vector<uint8_t> out;
+        try { orz::encode_stream(enc, be, src, n, false, out); } catch (const EmuBackend::Stop&) {}
+        if (!g_emu_tables.taken) return -2;
+        const size_t k = tr.pos.size() < cap ? tr.pos.size() : cap;
+        for (size_t i = 0; i < k; i++)
+            items[i] = EmuItem{tr.block[i], tr.pos[i], tr.src[i], tr.sym[i], tr.rank[i], tr.ctx[i], tr.mlen[i], tr.al[i], tr.unl[i], tr.enc[i]};
+        return (long)tr.pos.size();
+    } catch (const std::exception& e) {
+        g_emu_err = e.what();
+        return -1;
+    }
+}
+extern "C" long emu_fast_table(const char* name, void* dst, size_t cap) {
+    if (!name || !g_emu_tables.taken) return -1;
+    const std::vector<uint8_t>* t = g_emu_tables.find(name);
+    if (!t) return -1;
+    if (dst && cap) std::memcpy(dst, t->data(), std::min(cap, t->size()));
+    return (long)t->size();
+}
+// dist_valid (orz_fast.h) alone, for many (codes, budget) pairs
+extern "C" void emu_dist_valid_many(const unsigned long long* codes, const unsigned* budget, size_t n, unsigned* sure, unsigned* limit) {
+    for (size_t i = 0; i < n; i++) {
+        const orz::DistBracket b = orz::dist_valid(codes[i], budget[i]);
+        sure[i] = b.sure; limit[i] = b.limit;
+    }
+}
+// dist_code_up / dist_code_down (orz_fast.h) of the distances d0 .. d0 + n - 1
+extern "C" void emu_dist_codes(unsigned d0, size_t n, uint8_t* up, uint8_t* down) {
+    for (size_t i = 0; i < n; i++) {
+        up[i] = (uint8_t)orz::dist_code_up(d0 + (unsigned)i);
+        down[i] = (uint8_t)orz::dist_code_down(d0 + (unsigned)i);
     }
 }
 // the two bytes in front of the window after a stream was encoded (the context of the oldest history position looks there)
