@@ -238,6 +238,52 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
                                  size_t n_members, uint8_t* d_dst, size_t d_cap, size_t* dst_len, size_t* n_members_out,
                                  size_t* out_offs, orz_decode_stats* stats);
 
+/* ---- byte ranges of a members container (orz_decode_range.h) ------------------------------------------
+ * A reader indexes a container ONCE (on the device, as orz_decode_members_to_device does) and then serves reads of byte
+ * ranges of its DECODED data.  A read decodes only the members its non-empty ranges touch, each once per call however many
+ * ranges touch it, and each only as far as the furthest byte asked of it (decoding is causal: the first k bytes of a member
+ * need only the items that start before k), so what a read costs follows the bytes asked for, not the container: a member
+ * decodes at one lane's speed, and a range at a member's start costs a fraction of one at its end.  Nothing is kept between
+ * reads but the index and buffers.
+ *
+ * orz_reader_open: src / n / src_on_device / offs / lens / n_members exactly as for orz_decode_members_to_device.  A host
+ * container is uploaded and owned by the reader; a device container is BORROWED: the caller keeps it alive and unchanged until
+ * orz_reader_close.  NULL on failure, orz_last_error() as index errors read there (the first bad member is named).
+ * orz_reader_info: members, total decoded size and, when member_offs != NULL, the first `cap` members' decoded start offsets.
+ * orz_reader_read: n_ranges byte ranges [off[k], off[k] + len[k]) of the decoded data (member order, as
+ * orz_decode_members_to_device lays it out), in any order, overlapping, repeated and empty ranges allowed.  Their bytes are
+ * written back to back in range order at d_dst (d_cap bytes on the reader's device); *dst_len = the sum of len[].
+ *   ORZ_EINVAL, before anything reaches the device: a range with off + len above the total or overflowing 64 bits, NULL
+ *     arrays with n_ranges > 0, a device-resident container that overlaps [d_dst, d_dst + d_cap).
+ *   ORZ_ENOMEM: d_cap below the sum of the lengths.  Nothing is written; *dst_len is filled.
+ *   n_ranges == 0 or all lengths zero: ORZ_OK, *dst_len == 0, nothing is launched.
+ *   ORZ_EINVAL naming the member: payload damage BEFORE the furthest byte asked of a member (the content of the output is
+ *     then unspecified).  Damage behind that point is not seen and does not fail the read.
+ * The bytes equal the same slices of what orz_decode_members_mem returns and do not depend on what d_dst held; nothing outside
+ * [d_dst, d_dst + *dst_len) is written in any case.  A reader serves any number of reads and a failed read leaves it usable.
+ * Reads on one reader are SERIAL: a reader is not thread-safe (readers of their own are independent).  The host waits three
+ * times per read whatever the number of ranges: the upload of the ranges, one read of the plan's record, one read of the
+ * members' verdicts.  ORZ_DECODE_SLOTS bounds the members in flight as for orz_decode_members_device: more needed members
+ * than slots are several launches. */
+typedef struct orz_reader orz_reader;
+typedef struct {
+    uint64_t ranges;           /* ranges of the call */
+    uint64_t members_decoded;  /* distinct members touched by non-empty ranges */
+    uint64_t decoded_bytes;    /* bytes the decoder produced: per member the furthest byte asked, plus at most one item */
+    uint64_t out_bytes;        /* sum of the lengths */
+    uint64_t launches;         /* decode launches */
+    uint64_t host_waits;
+    double kernel_ms;          /* HIP-event time of the decode launches (sum) */
+    double gather_ms;          /* HIP-event time of the copy into d_dst */
+    double total_s;            /* wall time of the call */
+} orz_read_stats;
+orz_reader* orz_reader_open(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                            size_t n_members);
+void orz_reader_close(orz_reader*);
+int orz_reader_info(orz_reader*, uint64_t* members, uint64_t* total, uint64_t* member_offs, size_t cap);
+int orz_reader_read(orz_reader*, const uint64_t* off, const uint64_t* len, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
+                    uint64_t* dst_len, orz_read_stats* stats);
+
 /* The Huffman tables of `nchunks` chunks on the device, in the layout the encoder keeps them: a chunk is
  * orz_huffman_stride() = 389 + 389 + 240 entries (symbol ranks after a match / after a literal, long match lengths:
  * /root/reference/src/lz.rs:272-273,298-305), each of the three built as HuffmanTable::new_from_sym_weights(weights, 15)

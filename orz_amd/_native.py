@@ -84,6 +84,23 @@ class DecodeStats(ctypes.Structure):  # orz_decode_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReadStats(ctypes.Structure):  # orz_read_stats
+    _fields_ = [
+        ("ranges", ctypes.c_uint64),
+        ("members_decoded", ctypes.c_uint64),
+        ("decoded_bytes", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64),
+        ("launches", ctypes.c_uint64),
+        ("host_waits", ctypes.c_uint64),
+        ("kernel_ms", ctypes.c_double),
+        ("gather_ms", ctypes.c_double),
+        ("total_s", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 SYMBOLS = [
     ("orz_lzcfg_from_level", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LZCfg)]),
     ("orz_lz_encoder_new", ctypes.c_void_p, [ctypes.c_int]),
@@ -171,6 +188,24 @@ SYMBOLS = [
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
          ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(DecodeStats)],
+    ),
+    (
+        "orz_reader_open",
+        ctypes.c_void_p,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.c_size_t],
+    ),
+    ("orz_reader_close", None, [ctypes.c_void_p]),
+    (
+        "orz_reader_info",
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t],
+    ),
+    (
+        "orz_reader_read",
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_void_p,
+         ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ReadStats)],
     ),
     ("orz_stream_set_item_trace", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("orz_stream_get_item_trace", ctypes.c_long, [ctypes.c_void_p, ctypes.POINTER(Item), ctypes.c_size_t]),

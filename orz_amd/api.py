@@ -414,6 +414,102 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
     return tuple(res)
 
 
+class MemberReader:
+    """A members container opened ONCE for reads of byte ranges of its decoded data (orz_reader_*).  `src`: a uint8 torch tensor
+    on cuda:`device` (borrowed: the reader keeps a reference, do not change it while the reader lives) or on the CPU, or
+    bytes-like (uploaded).  `members`: None = `src` is one concatenation; else the [(offset, length)] list
+    MemberEncoder.encode_to_device returns.  A read decodes only the members its ranges touch, each only as far as the furthest
+    byte asked of it.  Reads are serial: not thread-safe."""
+
+    def __init__(self, src, device=0, members=None):
+        import torch
+
+        self._h = None
+        self._lib = _native.load()
+        self._dev = torch.device("cuda", int(device))
+        if isinstance(src, torch.Tensor):
+            if src.dtype != torch.uint8 or not src.is_contiguous():
+                raise ValueError("src must be a contiguous uint8 tensor")
+            if src.is_cuda and src.device != self._dev:
+                raise ValueError("src lies on %s, not on %s" % (src.device, self._dev))
+            keep, on_dev = src, src.is_cuda
+            ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
+        else:
+            data = bytes(src)
+            keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
+            ptr = ctypes.cast(keep, ctypes.c_void_p)
+        if members is None:
+            offs = lens = None
+            nt = 0
+        else:
+            nt = len(members)
+            offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
+            lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
+        torch.cuda.current_stream(self._dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        self._h = self._lib.orz_reader_open(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt)
+        if not self._h:
+            raise OrzError("orz_reader_open failed: %s" % _native.last_error())
+        self._keep = keep if on_dev else None  # (a host container was copied)
+        m, tot = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._lib.orz_reader_info(self._h, ctypes.byref(m), ctypes.byref(tot), None, 0), "orz_reader_info")
+        self.members, self.total = m.value, tot.value
+        self._offsets = None
+
+    @property
+    def member_offsets(self):
+        """where each member's bytes start in the decoded data"""
+        if self._offsets is None:
+            oo = (ctypes.c_uint64 * max(self.members, 1))()
+            _check(self._lib.orz_reader_info(self._h, None, None, oo, self.members), "orz_reader_info")
+            self._offsets = [oo[k] for k in range(self.members)]
+        return list(self._offsets)
+
+    def read_ranges(self, ranges, out=None, stats=False):
+        """the bytes of [(offset, length), ...] of the decoded data, back to back in that order, as a uint8 tensor on the device
+        (the first bytes of `out` when given: nothing else of it is written)[, stats dict]"""
+        import torch
+
+        if not self._h:
+            raise OrzError("the reader is closed")
+        if out is not None and (out.dtype != torch.uint8 or out.device != self._dev or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous uint8 tensor on %s" % self._dev)
+        ranges = [(int(o), int(ln)) for o, ln in ranges]
+        if any(o < 0 or ln < 0 or o >= 1 << 64 or ln >= 1 << 64 for o, ln in ranges):
+            raise ValueError("offsets and lengths are unsigned 64-bit numbers")
+        nr = len(ranges)
+        off = (ctypes.c_uint64 * max(nr, 1))(*[o for o, _ in ranges])
+        ln = (ctypes.c_uint64 * max(nr, 1))(*[l for _, l in ranges])
+        if out is None:
+            # (ranges the library will refuse get a buffer of one byte: the refusal comes from the library, with its message)
+            want = sum(l for o, l in ranges) if all(o + l <= self.total for o, l in ranges) else 0
+            out = torch.empty(want, dtype=torch.uint8, device=self._dev)
+        dst = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self._dev)
+        torch.cuda.current_stream(self._dev).synchronize()
+        dlen = ctypes.c_uint64()
+        st = _native.ReadStats()
+        rc = self._lib.orz_reader_read(self._h, off, ln, nr, ctypes.c_void_p(dst.data_ptr()), out.numel(), ctypes.byref(dlen),
+                                       ctypes.byref(st))
+        _check(rc, "orz_reader_read")
+        res = out[: dlen.value]
+        return (res, st.as_dict()) if stats else res
+
+    def read(self, offset, length, out=None, stats=False):
+        """`length` decoded bytes from `offset` (read_ranges of one range)"""
+        return self.read_ranges([(offset, length)], out=out, stats=stats)
+
+    def close(self):
+        if self._h:
+            self._lib.orz_reader_close(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def huffman_tables(weights, device=0):
     """Huffman code lengths and canonical codes of every table of `weights` ON THE GPU -- an array of shape
     [nchunks, orz_huffman_stride()] of symbol weights below 2^23 in the encoder's layout (389 + 389 + 240 symbols a chunk;

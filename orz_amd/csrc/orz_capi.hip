@@ -17,6 +17,7 @@
 #include "backend_hip.h"
 #include "orz_decode_device.h"
 #include "orz_decode_index.h"
+#include "orz_decode_range.h"
 #include "orz_host_decode.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
@@ -684,6 +685,71 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
     } catch (const std::exception& e) {
         return fail(ORZ_EINVAL, e.what());
     }
+}
+
+// ------------------------------------------------------------------------------ byte ranges of a container
+struct orz_reader {
+    std::unique_ptr<orz::HipBackend> be;
+    std::unique_ptr<orz::RangeReader<orz::HipBackend>> rd;  // (declared after the backend: destroyed before it)
+};
+
+orz_reader* orz_reader_open(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                            size_t n_members) {
+    if ((!src && n) || (!offs != !lens)) { fail(ORZ_EINVAL, "bad argument"); return nullptr; }
+    if (device < 0 || device >= orz_device_count()) { fail(ORZ_ENODEV, "no such HIP device"); return nullptr; }
+    try {
+        std::unique_ptr<orz_reader> r(new orz_reader);
+        r->be.reset(new orz::HipBackend(device));
+        r->rd.reset(new orz::RangeReader<orz::HipBackend>(*r->be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr,
+                                                          (const uint64_t*)offs, (const uint64_t*)lens, n_members));
+        return r.release();
+    } catch (const std::bad_alloc& e) {
+        fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        fail(ORZ_EINVAL, e.what());
+    }
+    return nullptr;
+}
+
+void orz_reader_close(orz_reader* r) { delete r; }
+
+int orz_reader_info(orz_reader* r, uint64_t* members, uint64_t* total, uint64_t* member_offs, size_t cap) {
+    if (!r) return fail(ORZ_EINVAL, "bad argument");
+    try {
+        if (members) *members = r->rd->ix.members;
+        if (total) *total = r->rd->ix.total;
+        if (member_offs && cap) {
+            const std::vector<uint64_t>& o = r->rd->member_offsets();
+            std::copy(o.begin(), o.begin() + std::min(cap, o.size()), member_offs);
+        }
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_EINVAL, e.what());
+    }
+}
+
+int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
+                    uint64_t* dst_len, orz_read_stats* stats) {
+    if (!r || !dst_len) return fail(ORZ_EINVAL, "bad argument");
+    orz::RangeReadStats st;
+    uint64_t total = 0;
+    int rc = ORZ_OK;
+    try {
+        r->rd->read(off, len, n_ranges, d_dst, d_cap, total, st, env_u("ORZ_DECODE_SLOTS", 2048));
+    } catch (const orz::DecodeCapacityError& e) {
+        rc = fail(ORZ_ENOMEM, e.what());
+    } catch (const std::bad_alloc& e) {
+        rc = fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        rc = fail(ORZ_EINVAL, e.what());
+    }
+    *dst_len = total;
+    if (stats) {
+        stats->ranges = st.ranges; stats->members_decoded = st.members_decoded; stats->decoded_bytes = st.decoded_bytes;
+        stats->out_bytes = st.out_bytes; stats->launches = st.launches; stats->host_waits = st.host_waits;
+        stats->kernel_ms = st.kernel_ms; stats->gather_ms = st.gather_ms; stats->total_s = st.total_s;
+    }
+    return rc;
 }
 
 // ------------------------------------------------------------------------------ Huffman tables alone

@@ -81,6 +81,10 @@ struct DecodeArgs {
     uint8_t* state;            // [slots] DecodeLayout::kBytes each, zeroed before the launch
     uint32_t* status;          // [members] kDec*
     uint32_t first, count;     // this launch decodes members first .. first + count - 1, one per block
+    // A partial decode (orz_decode_range.h); all three null = the whole member, which is what every other caller asks for.
+    const uint32_t* list = nullptr;  // block b decodes member list[first + b] instead of first + b
+    const uint32_t* stop = nullptr;  // [members] decode no further than this member offset: see run()
+    uint32_t* produced = nullptr;    // [members] the member offset the decode reached, at most out_len (written with kDecOk only)
 };
 
 // four bytes at any address, little-endian (the bit reader runs on the host too: index_members)
@@ -192,7 +196,7 @@ struct DecodeMember {
         l32[DecodeLds::kRecip / 4 + w.lane()] = 0xffffffffu / (327 + w.lane()) + 1;  // floor(n / d) == mulhi(n, floor(2^32 / d) + 1) for n < 2^17
         w.sync();
         if (w.lane() != 0) return;
-        const uint32_t m = a.first + w.block();
+        const uint32_t m = a.list ? a.list[a.first + w.block()] : a.first + w.block();
         a.status[m] = run(m, a.state + (size_t)w.block() * DecodeLayout::kBytes, w.lds());
     }
 
@@ -215,6 +219,17 @@ struct DecodeMember {
 
         uint8_t* out = a.out + a.out_off[m];       // out[i] is window position kPre + i
         const uint32_t out_len = a.out_len[m];
+        // With a stop the member ends, kDecOk, at the first chunk or item that STARTS at or beyond lim, and no byte at or beyond
+        // lim is stored or loaded: `out` need hold lim bytes only.  Decoding is causal, so the bytes below lim are those of the whole
+        // decode; what the stream holds behind that point is never looked at.  An item may start beyond lim and the member go on
+        // only inside a chunk whose end field lies below lim (its items overran the field, the cut below takes them back: crafted
+        // streams, no encoder's) -- bytes that are not stored read as zero there, as bytes beyond out_len always did.
+        const bool part = a.stop != nullptr;
+        const uint32_t lim = part && a.stop[m] < out_len ? a.stop[m] : out_len;
+        auto reached = [&](uint64_t mo) {
+            if (a.produced) a.produced[m] = mo < out_len ? (uint32_t)mo : out_len;
+            return (uint32_t)kDecOk;
+        };
         uint64_t at = a.m_begin[m];
         const uint64_t end = a.m_end[m];
         uint32_t spos = kPre;                       // window offset, as the reference counts it
@@ -222,6 +237,7 @@ struct DecodeMember {
         uint64_t tail = 0;                          // the last eight decoded bytes, newest in the low byte
         bool first = true, after_literal = true;
         for (;;) {
+            if (part && spos - kPre + slid >= lim) return reached(spos - kPre + slid);
             // chunk length, LEB128 (read_len, src/ioutil.rs:60-77); 0 = end of stream
             uint64_t t = 0;
             for (uint32_t sh = 0;; sh += 7) {
@@ -264,7 +280,9 @@ struct DecodeMember {
                 if (ml[k] == 99) return kDecBadData;
                 if (ml[k] == 98) return kDecDeepTable;
             }
+            const bool may_stop = part && (uint64_t)end_field + slid >= (uint64_t)lim + kPre;  // (no cut of this chunk goes back below lim)
             for (uint32_t it = 0; it < n_items; it++) {
+                if (may_stop && spos - kPre + slid >= lim) return reached(spos - kPre + slid);
                 const uint32_t r = sym(br, lut + (after_literal ? 32768 : 0), prim + (after_literal ? 4096 : 0), ml[after_literal ? 1 : 0]);
                 if (r >= kSyms) return kDecBadData;
                 // hash1(spos-1), hash2(spos-1) from the last three bytes (src/lz.rs:482-492)
@@ -324,12 +342,12 @@ struct DecodeMember {
                 uint32_t ro = 0, len = 0, mn_raw = 0;  // (mn_raw: the source node's len_min as the match read it -- its update below needs no second load)
                 bool match = false;
                 if (v == kWordSym) {
-                    out[opos] = w0;
-                    if (opos + 1 < out_len) out[opos + 1] = w1;
+                    if (opos < lim) out[opos] = w0;
+                    if (opos + 1 < lim) out[opos + 1] = w1;
                     tail = (tail << 16) | ((uint64_t)w0 << 8) | w1;
                     after_literal = false;
                 } else if (v < 256) {
-                    out[opos] = (uint8_t)v;
+                    if (opos < lim) out[opos] = (uint8_t)v;
                     tail = (tail << 8) | v;
                     after_literal = true;
                 } else {
@@ -353,7 +371,7 @@ struct DecodeMember {
                     if (srec == 0 || (uint64_t)(srec - 1) + kPre <= (uint64_t)slid || srec - 1 >= opos || len > kMaxLen + 127) return kDecBadData;
                     const uint32_t src = srec - 1;
                     const uint32_t len8 = (len + 7) & ~7u;
-                    if (src + len8 <= opos && opos + len <= out_len) {
+                    if (src + len8 <= opos && opos + len <= lim) {
                         // the source lies wholly before the item (and the last load's spare bytes too): eight bytes a load, the loads
                         // of 32 bytes asked for together before their stores (mem_fast_copy, src/mem.rs:74-92, for a lane); the
                         // register of the last eight bytes from one more load of the source's end
@@ -376,8 +394,8 @@ struct DecodeMember {
                     } else {
                         for (uint32_t k = 0; k < len; k++) {  // overlap-safe forward copy
                             const uint32_t sp = src + k;
-                            const uint8_t b = sp < out_len ? out[sp] : 0;
-                            if (opos + k < out_len) out[opos + k] = b;
+                            const uint8_t b = sp < lim ? out[sp] : 0;
+                            if (opos + k < lim) out[opos + k] = b;
                             tail = (tail << 8) | b;
                         }
                     }
@@ -411,6 +429,7 @@ struct DecodeMember {
                 if (spos >= kPre) {
                     const uint64_t mo = (uint64_t)spos - kPre + slid;
                     if (mo > out_len) return kDecSizeMismatch;  // (a cut that lands past the member's region -- those bytes were never stored)
+                    if (part && mo >= lim) return reached(mo);
                     tail = 0;
                     for (uint32_t k = 8; k >= 1; k--) tail = (tail << 8) | (mo >= k ? (uint64_t)out[mo - k] : 0);
                 }
@@ -422,6 +441,7 @@ struct DecodeMember {
                 spos = kPre;
             }
         }
+        if (part) return spos - kPre + slid >= lim ? reached(spos - kPre + slid) : (uint32_t)kDecSizeMismatch;  // (a stream that ends short of the bytes asked for)
         return spos - kPre + slid == out_len ? kDecOk : kDecSizeMismatch;
     }
 };
