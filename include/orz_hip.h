@@ -244,7 +244,7 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
  * ranges touch it, and each only as far as the furthest byte asked of it (decoding is causal: the first k bytes of a member
  * need only the items that start before k), so what a read costs follows the bytes asked for, not the container: a member
  * decodes at one lane's speed, and a range at a member's start costs a fraction of one at its end.  Nothing is kept between
- * reads but the index and buffers.
+ * reads but the index and buffers, unless the caller gives the reader a budget for cursors (orz_reader_set_cache, below).
  *
  * orz_reader_open: src / n / src_on_device / offs / lens / n_members exactly as for orz_decode_members_to_device.  A host
  * container is uploaded and owned by the reader; a device container is BORROWED: the caller keeps it alive and unchanged until
@@ -268,8 +268,9 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
 typedef struct orz_reader orz_reader;
 typedef struct {
     uint64_t ranges;           /* ranges of the call */
-    uint64_t members_decoded;  /* distinct members touched by non-empty ranges */
-    uint64_t decoded_bytes;    /* bytes the decoder produced: per member the furthest byte asked, plus at most one item */
+    uint64_t members_decoded;  /* distinct members touched by non-empty ranges (with cursors: those a decode ran for) */
+    uint64_t decoded_bytes;    /* bytes the decoder produced: per member the furthest byte asked, plus at most one item (with
+                                  cursors: the bytes NEWLY produced in this call) */
     uint64_t out_bytes;        /* sum of the lengths */
     uint64_t launches;         /* decode launches */
     uint64_t host_waits;
@@ -283,6 +284,32 @@ void orz_reader_close(orz_reader*);
 int orz_reader_info(orz_reader*, uint64_t* members, uint64_t* total, uint64_t* member_offs, size_t cap);
 int orz_reader_read(orz_reader*, const uint64_t* off, const uint64_t* len, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
                     uint64_t* dst_len, orz_read_stats* stats);
+
+/* CURSORS (opt-in).  Without them every read starts every member it touches at byte 0, so walking through a member window by
+ * window decodes its beginning again and again.  With a budget a reader keeps cursors: a member's decoded prefix in device
+ * memory together with the decoder's state at its end, so a later read costs only the bytes not yet decoded and nothing for
+ * bytes that are there (a second read of a range, a seek backwards).
+ * orz_reader_set_cache: the budget in bytes of device memory; 0 = off, the default: every cursor is freed and a read is exactly
+ *   what it is without this call.  A smaller budget evicts least recently touched cursors until the rest fits.
+ * orz_reader_cursor_state_bytes: a cursor of a member that decodes to n bytes costs n rounded up to 256 plus this constant (the
+ *   decoder's tables, a copy of its LDS, its registers: about 7.4 MB).  A budget below that of the members read keeps nothing.
+ * Policy, over the members a call touches, in ascending member order: a cursor that holds the furthest byte asked of its member is
+ * a HIT (no decode); one that falls short is RESUMED; a member without one gets a FRESH cursor if its cost fits the budget after
+ * evicting least recently touched cursors that the call does not touch (ties: the lower member; nothing is evicted unless that
+ * makes room), and is otherwise decoded as without the cache and nothing is kept (UNCACHED; so is a member whose cursor cannot
+ * be allocated: not an error).  A member whose decode fails loses its cursor; the read reports ORZ_EINVAL naming it as above and
+ * the reader stays usable.  Damage behind the furthest byte asked is still not seen.
+ * With the cache on, orz_read_stats.decoded_bytes counts the bytes the decoder NEWLY produced in the call (0 for hits),
+ * members_decoded the members a decode ran for (resumed + fresh + uncached), launches is 0 when every touched member is a hit,
+ * and the host waits twice per read, whatever the ranges: the upload of the ranges and of the plan (made on the host from the
+ * member offsets), and the read of the members' verdicts. */
+typedef struct {
+    uint64_t hits, resumed, fresh, uncached, evicted; /* of the last read, in members (all 0 while the cache is off) */
+    uint64_t cursors, bytes, budget;                  /* now: cursors held, what they cost, orz_reader_set_cache's value */
+} orz_cache_stats;
+int orz_reader_set_cache(orz_reader*, uint64_t max_bytes);
+uint64_t orz_reader_cursor_state_bytes(void);
+int orz_reader_cache_stats(orz_reader*, orz_cache_stats* stats);
 
 /* The Huffman tables of `nchunks` chunks on the device, in the layout the encoder keeps them: a chunk is
  * orz_huffman_stride() = 389 + 389 + 240 entries (symbol ranks after a match / after a literal, long match lengths:

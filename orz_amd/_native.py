@@ -101,6 +101,13 @@ class ReadStats(ctypes.Structure):  # orz_read_stats
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CacheStats(ctypes.Structure):  # orz_cache_stats
+    _fields_ = [(k, ctypes.c_uint64) for k in ("hits", "resumed", "fresh", "uncached", "evicted", "cursors", "bytes", "budget")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 SYMBOLS = [
     ("orz_lzcfg_from_level", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(LZCfg)]),
     ("orz_lz_encoder_new", ctypes.c_void_p, [ctypes.c_int]),
@@ -207,6 +214,9 @@ SYMBOLS = [
         [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_void_p,
          ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ReadStats)],
     ),
+    ("orz_reader_set_cache", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    ("orz_reader_cursor_state_bytes", ctypes.c_uint64, []),
+    ("orz_reader_cache_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CacheStats)]),
     ("orz_stream_set_item_trace", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("orz_stream_get_item_trace", ctypes.c_long, [ctypes.c_void_p, ctypes.POINTER(Item), ctypes.c_size_t]),
     ("orz_stream_fast_tables", ctypes.c_long, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]),

@@ -419,9 +419,13 @@ class MemberReader:
     on cuda:`device` (borrowed: the reader keeps a reference, do not change it while the reader lives) or on the CPU, or
     bytes-like (uploaded).  `members`: None = `src` is one concatenation; else the [(offset, length)] list
     MemberEncoder.encode_to_device returns.  A read decodes only the members its ranges touch, each only as far as the furthest
-    byte asked of it.  Reads are serial: not thread-safe."""
+    byte asked of it.  Reads are serial: not thread-safe.
+    `cache_bytes`: a budget of device memory for CURSORS (0 = none, the default): a member's decoded prefix kept with the decoder's
+    state at its end, so that a later read decodes only what is not there yet -- walking through a member window by window
+    decodes it once, reading a range again or seeking backwards decodes nothing.  A cursor costs the member's decoded size
+    rounded up to 256 plus MemberReader.cursor_state_bytes()."""
 
-    def __init__(self, src, device=0, members=None):
+    def __init__(self, src, device=0, members=None, cache_bytes=0):
         import torch
 
         self._h = None
@@ -454,6 +458,30 @@ class MemberReader:
         _check(self._lib.orz_reader_info(self._h, ctypes.byref(m), ctypes.byref(tot), None, 0), "orz_reader_info")
         self.members, self.total = m.value, tot.value
         self._offsets = None
+        if cache_bytes:
+            self.set_cache(cache_bytes)
+
+    @staticmethod
+    def cursor_state_bytes():
+        """what a cursor costs of the budget beyond its member's decoded bytes"""
+        return _native.load().orz_reader_cursor_state_bytes()
+
+    def set_cache(self, nbytes):
+        """the budget for cursors in bytes; 0 switches the cache off and frees every cursor, a smaller budget evicts the least
+        recently touched ones"""
+        if not self._h:
+            raise OrzError("the reader is closed")
+        if int(nbytes) < 0 or int(nbytes) >= 1 << 64:
+            raise ValueError("the budget is an unsigned 64-bit number")
+        _check(self._lib.orz_reader_set_cache(self._h, int(nbytes)), "orz_reader_set_cache")
+
+    def cache_stats(self):
+        """{hits, resumed, fresh, uncached, evicted} of the last read in members, and {cursors, bytes, budget} now"""
+        if not self._h:
+            raise OrzError("the reader is closed")
+        st = _native.CacheStats()
+        _check(self._lib.orz_reader_cache_stats(self._h, ctypes.byref(st)), "orz_reader_cache_stats")
+        return st.as_dict()
 
     @property
     def member_offsets(self):

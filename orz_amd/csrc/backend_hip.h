@@ -349,7 +349,11 @@ class HipBackend {
         void* p = arena_take(bytes);
         if (!p) {
             ORZ_HIP_CHECK(hipSetDevice(device_));
-            ORZ_HIP_CHECK(hipMalloc(&p, bytes));
+            const hipError_t e = hipMalloc(&p, bytes);
+            if (e != hipSuccess) {  // (a caller that does without the buffer goes on: the next launch's check must not find this error)
+                (void)hipGetLastError();
+                throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " at hipMalloc(&p, bytes)");
+            }
         }
         if (zero) ORZ_HIP_CHECK(hipMemsetAsync(p, 0, bytes, stream_));
         return (T*)p;

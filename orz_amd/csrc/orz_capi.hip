@@ -752,6 +752,28 @@ int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, siz
     return rc;
 }
 
+int orz_reader_set_cache(orz_reader* r, uint64_t max_bytes) {
+    if (!r) return fail(ORZ_EINVAL, "bad argument");
+    try {
+        r->rd->set_cache(max_bytes);
+        return ORZ_OK;
+    } catch (const std::bad_alloc& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        return fail(ORZ_EINVAL, e.what());
+    }
+}
+
+uint64_t orz_reader_cursor_state_bytes(void) { return orz::RangeReader<orz::HipBackend>::cursor_state_bytes(); }
+
+int orz_reader_cache_stats(orz_reader* r, orz_cache_stats* stats) {
+    if (!r || !stats) return fail(ORZ_EINVAL, "bad argument");
+    const orz::RangeCacheStats c = r->rd->cache_stats();
+    stats->hits = c.hits; stats->resumed = c.resumed; stats->fresh = c.fresh; stats->uncached = c.uncached; stats->evicted = c.evicted;
+    stats->cursors = c.cursors; stats->bytes = c.bytes; stats->budget = c.budget;
+    return ORZ_OK;
+}
+
 // ------------------------------------------------------------------------------ Huffman tables alone
 size_t orz_huffman_stride(void) { return orz::kHwStride; }
 int orz_huffman_tables(int device, const uint32_t* weights, size_t nchunks, uint8_t* lens, uint16_t* codes, double* elapsed_us) {

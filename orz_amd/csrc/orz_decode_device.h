@@ -71,6 +71,32 @@ struct DecodeLds {  // byte offsets into a member's LDS (DecodeMember::lds_bytes
 };
 constexpr uint16_t kDecLong = 0xffff;  // (no real entry: a symbol is below 512 and a length below 16)
 
+// What run() keeps in registers wherever a decode with a stop ends with kDecOk: with the member's blob and its LDS this is the
+// whole state of the decoder, so a later launch goes on from there (a CURSOR, orz_decode_range.h).  live == 0: a decode from the
+// member's first byte.
+struct DecodeResume {
+    uint32_t live, in_chunk;   // in_chunk: between two items of the chunk that `br` reads, item `it` of n_items comes next
+    uint64_t at;               // container offset of the next chunk-length prefix
+    uint64_t br_off;           // the open chunk's payload, as a container offset (Bits::p)
+    uint64_t br_acc;
+    uint32_t br_n, br_at, br_have;
+    uint32_t end_field, n_items, it;
+    uint32_t ml[3];
+    uint32_t spos, slid;
+    uint32_t first, after_literal;
+    uint64_t tail;
+};
+
+// One cursor's memory: the member's decoded bytes (its announced size, rounded up to 256), then the blob, the copy of the LDS and
+// the record.  DecodeArgs::cursor names the blob; the bytes are found through DecodeArgs::out_off as any member's are.
+struct DecodeCursor {
+    static constexpr size_t kBlob = 0;
+    static constexpr size_t kSpill = DecodeLayout::kBytes;                               // DecodeLds::kBytes, a multiple of 16
+    static constexpr size_t kRecord = kSpill + (DecodeLds::kBytes + 255) / 256 * 256;
+    static constexpr size_t kBytes = kRecord + 256;
+};
+static_assert(sizeof(DecodeResume) <= 256 && DecodeLds::kBytes % 16 == 0 && DecodeLayout::kBytes % 256 == 0, "a cursor's layout");
+
 struct DecodeArgs {
     const uint8_t* src;        // the container
     const uint64_t* m_begin;   // [members] offset of the member's first chunk-length prefix
@@ -85,6 +111,13 @@ struct DecodeArgs {
     const uint32_t* list = nullptr;  // block b decodes member list[first + b] instead of first + b
     const uint32_t* stop = nullptr;  // [members] decode no further than this member offset: see run()
     uint32_t* produced = nullptr;    // [members] the member offset the decode reached, at most out_len (written with kDecOk only)
+    // Cursors (DecodeMemberCursor alone looks at this; null for every other caller).
+    // [launch slots, indexed as `list` is] 0, or the address of a DecodeCursor's blob: the decode starts from the cursor's record
+    // (from byte 0 when the record is not live; the host zeroed blob, spill and record then), STORES every item whole up to out_len
+    // (the member's place holds out_len bytes) and stops as `stop` says; when it stops with kDecOk it leaves record and LDS in the
+    // cursor.  Needs `stop`.  After any other status the cursor's content is unspecified.
+    // (Members whose bytes lie in buffers of their own need no field: out_off[m] is the member's address minus `out`, modulo 2^64.)
+    const uint64_t* cursor = nullptr;
 };
 
 // four bytes at any address, little-endian (the bit reader runs on the host too: index_members)
@@ -98,7 +131,19 @@ ORZ_HD uint32_t dec_ld32(const uint8_t* p) {
 #endif
 }
 
-struct DecodeMember {
+// sixteen bytes at addresses that are multiples of 16
+ORZ_HD void dec_copy16(uint8_t* d, const uint8_t* s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
+#else
+    __builtin_memcpy(d, s, 16);
+#endif
+}
+
+// kCursor = false is the decoder every caller but the cursor cache launches (DecodeMember): DecodeArgs::cursor is not looked at
+// and everything that serves cursors folds away, so that kernel is what it was before cursors existed.
+template <bool kCursor>
+struct DecodeMemberBody {
     DecodeArgs a;
 
     struct Bits {  // MSB-first bit reader over big-endian 32-bit words (src/coder.rs:159-217)
@@ -190,17 +235,31 @@ struct DecodeMember {
     template <class W>
     ORZ_D void operator()(W& w) const {
         if (w.block() >= a.count) return;
-        uint32_t* l32 = (uint32_t*)w.lds();  // words[] and the ring heads start at zero (LZContext::new, src/lz.rs:57-66): all lanes clear them
-        for (uint32_t i = w.lane(); i < DecodeLds::kBytes / 4; i += 64) l32[i] = 0;
+        // (uniform over the wavefront: every lane of a block reads the same slot)
+        uint8_t* cur = kCursor && a.cursor ? (uint8_t*)(uintptr_t)a.cursor[a.first + w.block()] : nullptr;
+        DecodeResume* rec = cur ? (DecodeResume*)(cur + DecodeCursor::kRecord) : nullptr;
+        uint32_t* l32 = (uint32_t*)w.lds();
+        if (rec && rec->live) {  // the LDS as the launch that stopped left it (written by that launch, read by this one: DESIGN.md 2a), 16 bytes a lane
+            for (uint32_t i = w.lane(); i < DecodeLds::kBytes / 16; i += 64) dec_copy16(w.lds() + (size_t)i * 16, cur + DecodeCursor::kSpill + (size_t)i * 16);
+        } else {  // words[] and the ring heads start at zero (LZContext::new, src/lz.rs:57-66): all lanes clear them
+            for (uint32_t i = w.lane(); i < DecodeLds::kBytes / 4; i += 64) l32[i] = 0;
+        }
         w.sync();
         l32[DecodeLds::kRecip / 4 + w.lane()] = 0xffffffffu / (327 + w.lane()) + 1;  // floor(n / d) == mulhi(n, floor(2^32 / d) + 1) for n < 2^17
         w.sync();
-        if (w.lane() != 0) return;
-        const uint32_t m = a.list ? a.list[a.first + w.block()] : a.first + w.block();
-        a.status[m] = run(m, a.state + (size_t)w.block() * DecodeLayout::kBytes, w.lds());
+        if (!kCursor && w.lane() != 0) return;
+        if (w.lane() == 0) {
+            const uint32_t m = a.list ? a.list[a.first + w.block()] : a.first + w.block();
+            a.status[m] = run(m, cur ? cur + DecodeCursor::kBlob : a.state + (size_t)w.block() * DecodeLayout::kBytes, w.lds(), rec);
+        }
+        if (!cur) return;
+        // the one place where the other 63 lanes work: lane 0 is done, the LDS goes to the cursor in a few coalesced passes
+        w.sync();
+        for (uint32_t i = w.lane(); i < DecodeLds::kBytes / 16; i += 64) dec_copy16(cur + DecodeCursor::kSpill + (size_t)i * 16, w.lds() + (size_t)i * 16);
     }
 
-    ORZ_HD uint32_t run(uint32_t m, uint8_t* st, uint8_t* lds) const {
+    ORZ_HD uint32_t run(uint32_t m, uint8_t* st, uint8_t* lds, DecodeResume* rec_in = nullptr) const {
+        DecodeResume* const rec = kCursor ? rec_in : nullptr;
         uint32_t* ring_pos = (uint32_t*)(st + DecodeLayout::kRingPos);
         uint8_t* ring_min = st + DecodeLayout::kRingMin;
         uint8_t* ring_exp = st + DecodeLayout::kRingExp;
@@ -215,7 +274,9 @@ struct DecodeMember {
         uint16_t* lut = (uint16_t*)(st + DecodeLayout::kLut);
         uint8_t* lens = st + DecodeLayout::kLens;
         uint16_t* order = (uint16_t*)(st + DecodeLayout::kOrder);
-        for (uint32_t c = 0; c < 512; c++) rank_sum[c] = 1000000;  // SymRankCoder::new, src/symrank.rs:22-29
+        const bool resumed = rec && rec->live;
+        if (!resumed)
+            for (uint32_t c = 0; c < 512; c++) rank_sum[c] = 1000000;  // SymRankCoder::new, src/symrank.rs:22-29
 
         uint8_t* out = a.out + a.out_off[m];       // out[i] is window position kPre + i
         const uint32_t out_len = a.out_len[m];
@@ -224,21 +285,48 @@ struct DecodeMember {
         // decode; what the stream holds behind that point is never looked at.  An item may start beyond lim and the member go on
         // only inside a chunk whose end field lies below lim (its items overran the field, the cut below takes them back: crafted
         // streams, no encoder's) -- bytes that are not stored read as zero there, as bytes beyond out_len always did.
+        //
+        // A CURSOR (rec != nullptr) separates the two things lim is: the decode SUSPENDS at the first chunk or item that starts at or
+        // beyond the stop (slim), and stores every item whole up to out_len (lim).  A decode that is thrown away may leave the bytes
+        // of its last item beyond the stop unstored although spos and tail have moved past them; one that goes on later would copy
+        // matches out of that hole.  So a cursor's buffer holds out_len bytes, and `produced` is the number of valid ones.
         const bool part = a.stop != nullptr;
-        const uint32_t lim = part && a.stop[m] < out_len ? a.stop[m] : out_len;
-        auto reached = [&](uint64_t mo) {
-            if (a.produced) a.produced[m] = mo < out_len ? (uint32_t)mo : out_len;
-            return (uint32_t)kDecOk;
-        };
+        const uint32_t slim = part && a.stop[m] < out_len ? a.stop[m] : out_len;
+        const uint32_t lim = rec ? out_len : slim;
         uint64_t at = a.m_begin[m];
         const uint64_t end = a.m_end[m];
         uint32_t spos = kPre;                       // window offset, as the reference counts it
         uint32_t slid = 0;                          // bytes the window has slid by so far: window offset x is member offset x - kPre + slid
         uint64_t tail = 0;                          // the last eight decoded bytes, newest in the low byte
         bool first = true, after_literal = true;
+        Bits br{a.src, 0, 0, 0, 0};
+        uint32_t end_field = 0, n_items = 0, it = 0;
+        uint32_t ml[3] = {0, 0, 0};
+        // where the decode ends with kDecOk: how far it came and, for a cursor, everything the next launch needs to go on from here
+        auto reached = [&](uint64_t mo, bool in_chunk, uint64_t next) {
+            if (a.produced) a.produced[m] = mo < out_len ? (uint32_t)mo : out_len;
+            if constexpr (kCursor) if (rec) {
+                rec->live = 1; rec->in_chunk = in_chunk; rec->at = next;
+                rec->br_off = (uint64_t)(br.p - a.src); rec->br_acc = br.acc; rec->br_n = br.n; rec->br_at = br.at; rec->br_have = br.have;
+                rec->end_field = end_field; rec->n_items = n_items; rec->it = it;
+                rec->ml[0] = ml[0]; rec->ml[1] = ml[1]; rec->ml[2] = ml[2];
+                rec->spos = spos; rec->slid = slid; rec->first = first; rec->after_literal = after_literal; rec->tail = tail;
+            }
+            return (uint32_t)kDecOk;
+        };
+        bool in_chunk = false;  // (only ever true on the way into the first pass of the loop below)
+        if (resumed) {
+            in_chunk = rec->in_chunk != 0; at = rec->at;
+            br = Bits{a.src + rec->br_off, rec->br_n, rec->br_at, rec->br_acc, rec->br_have};
+            end_field = rec->end_field; n_items = rec->n_items; it = rec->it;
+            ml[0] = rec->ml[0]; ml[1] = rec->ml[1]; ml[2] = rec->ml[2];
+            spos = rec->spos; slid = rec->slid; first = rec->first != 0; after_literal = rec->after_literal != 0; tail = rec->tail;
+        }
         for (;;) {
-            if (part && spos - kPre + slid >= lim) return reached(spos - kPre + slid);
+          if (!in_chunk) {
+            if (part && spos - kPre + slid >= slim) return reached(spos - kPre + slid, false, at);
             // chunk length, LEB128 (read_len, src/ioutil.rs:60-77); 0 = end of stream
+            const uint64_t at0 = at;
             uint64_t t = 0;
             for (uint32_t sh = 0;; sh += 7) {
                 if (at >= end || sh > 56) return kDecBadData;
@@ -246,9 +334,9 @@ struct DecodeMember {
                 t |= (uint64_t)(b & 0x7f) << sh;
                 if (!(b & 0x80)) break;
             }
-            if (t == 0) break;
+            if (t == 0) { at = at0; break; }  // (a cursor that is asked again reads the end of the stream again)
             if (t >= (uint64_t)kPre * 3 || at + t > end) return kDecBadData;  // src/lib.rs:111-113
-            Bits br{a.src + at, (uint32_t)t, 0, 0, 0};
+            br = Bits{a.src + at, (uint32_t)t, 0, 0, 0};
             at += t;
             bool bad = false;
             if (first) {  // census order, src/lz.rs:372-392
@@ -271,18 +359,20 @@ struct DecodeMember {
                     }
                 first = false;
             }
-            const uint32_t end_field = br.varint(bad);
-            const uint32_t n_items = br.varint(bad);
+            end_field = br.varint(bad);
+            n_items = br.varint(bad);
             if (bad) return kDecBadData;
-            uint32_t ml[3];
             for (int k = 0; k < 3; k++) {
                 ml[k] = read_table(br, lens, lut + (size_t)k * 32768, prim + (size_t)k * 4096);
                 if (ml[k] == 99) return kDecBadData;
                 if (ml[k] == 98) return kDecDeepTable;
             }
-            const bool may_stop = part && (uint64_t)end_field + slid >= (uint64_t)lim + kPre;  // (no cut of this chunk goes back below lim)
-            for (uint32_t it = 0; it < n_items; it++) {
-                if (may_stop && spos - kPre + slid >= lim) return reached(spos - kPre + slid);
+            it = 0;
+          }
+            in_chunk = false;
+            const bool may_stop = part && (uint64_t)end_field + slid >= (uint64_t)slim + kPre;  // (no cut of this chunk goes back below the stop)
+            for (; it < n_items; it++) {
+                if (may_stop && spos - kPre + slid >= slim) return reached(spos - kPre + slid, true, at);
                 const uint32_t r = sym(br, lut + (after_literal ? 32768 : 0), prim + (after_literal ? 4096 : 0), ml[after_literal ? 1 : 0]);
                 if (r >= kSyms) return kDecBadData;
                 // hash1(spos-1), hash2(spos-1) from the last three bytes (src/lz.rs:482-492)
@@ -429,7 +519,9 @@ struct DecodeMember {
                 if (spos >= kPre) {
                     const uint64_t mo = (uint64_t)spos - kPre + slid;
                     if (mo > out_len) return kDecSizeMismatch;  // (a cut that lands past the member's region -- those bytes were never stored)
-                    if (part && mo >= lim) return reached(mo);
+                    // (a cursor goes on: its bytes below mo are stored, so the register is rebuilt here and the decode suspends at
+                    // the top of the loop, before the next chunk's length)
+                    if (part && !rec && mo >= slim) return reached(mo, false, at);
                     tail = 0;
                     for (uint32_t k = 8; k >= 1; k--) tail = (tail << 8) | (mo >= k ? (uint64_t)out[mo - k] : 0);
                 }
@@ -441,11 +533,12 @@ struct DecodeMember {
                 spos = kPre;
             }
         }
-        if (part) return spos - kPre + slid >= lim ? reached(spos - kPre + slid) : (uint32_t)kDecSizeMismatch;  // (a stream that ends short of the bytes asked for)
+        if (part) return spos - kPre + slid >= slim ? reached(spos - kPre + slid, false, at) : (uint32_t)kDecSizeMismatch;  // (a stream that ends short of the bytes asked for)
         return spos - kPre + slid == out_len ? kDecOk : kDecSizeMismatch;
     }
 };
-
+struct DecodeMember : DecodeMemberBody<false> {};
+struct DecodeMemberCursor : DecodeMemberBody<true> {};  // (the launches of a read with the cursor cache on)
 
 // ------------------------------------------------------------------------------------------------ host side
 struct DecodeStats {

@@ -11,7 +11,16 @@
 // RangeGather -> [host reads stops, statuses and what was produced]: the upload and two reads, however many ranges.  The rule of
 // DESIGN.md 2a holds: a thread acts only on state that an earlier launch wrote (stop[] is cleared before RangePlan raises it,
 // with atomic maxima, whose result does not depend on the order of the lanes).
+//
+// CURSORS (opt-in: set_cache).  Every read above starts every member it touches at byte 0, so walking through a member window by
+// window is quadratic.  The decoder is causal and its whole state is explicit (the blob, the LDS, a handful of registers:
+// DecodeResume), so a reader may keep, under a byte budget, a member's decoded prefix together with the decoder state at its
+// end, and a later read costs the bytes not yet decoded.  With the cache on a read is planned on the HOST from the member offsets
+// the reader has: upload (ranges and the per-member plan in one copy) -> clear -> DecodeMember launches over the members that
+// fall short -> RangeGather -> [host reads statuses and what was produced]: two host waits.  With the cache off a read is what it
+// was, launch for launch.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -108,7 +117,7 @@ struct RangeCompact {
 struct RangeGather {
     const uint64_t *off, *prefix;  // [n_ranges], [n_ranges + 1]: prefix[k] = sum of len[0 .. k)
     uint64_t n_ranges;
-    const uint64_t *out_off, *arena_off;
+    const uint64_t *out_off, *arena_off;  // (arena_off[m]: where a touched member's bytes lie, relative to `arena`, modulo 2^64: cursors' are buffers of their own)
     const uint32_t *out_len, *status;
     uint64_t members;
     const uint8_t* arena;
@@ -145,6 +154,11 @@ struct RangeReadStats {
     double kernel_ms = 0, gather_ms = 0, total_s = 0;
 };
 
+struct RangeCacheStats {
+    uint64_t hits = 0, resumed = 0, fresh = 0, uncached = 0, evicted = 0;  // of the last read (all zero while the cache is off)
+    uint64_t cursors = 0, bytes = 0, budget = 0;                           // now
+};
+
 // Thrown for what the caller got wrong (ORZ_EINVAL before anything reaches the device).
 struct RangeArgumentError : std::runtime_error {
     using std::runtime_error::runtime_error;
@@ -172,6 +186,19 @@ struct RangeReader {
     uint8_t* state = nullptr;
     uint32_t state_slots = 0;
     std::vector<uint64_t> h_off;  // (orz_reader_info: read once, on demand)
+    // the cursor cache (set_cache): off while budget == 0
+    struct Cursor {
+        uint32_t m;
+        uint8_t* mem;       // the member's bytes (out_len rounded up to 256), then a DecodeCursor
+        uint64_t cost;
+        uint32_t produced;  // valid bytes at mem
+        uint64_t touched;   // the read that touched it last
+    };
+    std::vector<Cursor> cursors;  // ascending in m
+    uint64_t budget = 0, held = 0, reads = 0;
+    RangeCacheStats last;
+    uint8_t* d_up = nullptr;  // one upload a read: off | len | prefix | place[M] | cursor[M] (u64), stop[M] | list[M] (u32)
+    size_t up_cap = 0;
 
     RangeReader(BE& b, const uint8_t* src, size_t n_, bool src_on_device, bool table, const uint64_t* offs, const uint64_t* lens,
                 size_t n_table)
@@ -199,9 +226,12 @@ struct RangeReader {
     RangeReader& operator=(const RangeReader&) = delete;
     ~RangeReader() { release(); }
     void release() {
-        for (void* p : {(void*)owned_src, (void*)plan, (void*)rec, (void*)d_ranges, (void*)arena, (void*)state})
+        for (void* p : {(void*)owned_src, (void*)plan, (void*)rec, (void*)d_ranges, (void*)arena, (void*)state, (void*)d_up})
             if (p) be.free(p);
-        owned_src = plan = arena = state = nullptr;
+        for (Cursor& c : cursors) be.free(c.mem);
+        cursors.clear();
+        held = 0;
+        owned_src = plan = arena = state = d_up = nullptr;
         rec = nullptr;
         d_ranges = nullptr;
     }
@@ -227,6 +257,44 @@ struct RangeReader {
         if (p) be.free(p);
         p = q;
         cap = want;
+    }
+
+    // ---- cursors
+    // What a cursor costs beyond its member's bytes: the blob, the copy of the LDS, the record.
+    static uint64_t cursor_state_bytes() { return DecodeCursor::kBytes; }
+    static uint64_t cursor_cost(uint32_t out_len) { return ((uint64_t)out_len + 255) / 256 * 256 + cursor_state_bytes(); }
+    uint32_t member_len(uint64_t m) const { return (uint32_t)((m + 1 < ix.members ? h_off[m + 1] : ix.total) - h_off[m]); }
+    Cursor* find_cursor(uint32_t m) {
+        auto it = std::lower_bound(cursors.begin(), cursors.end(), m, [](const Cursor& c, uint32_t x) { return c.m < x; });
+        return it != cursors.end() && it->m == m ? &*it : nullptr;
+    }
+    void drop_cursor(uint32_t m) {
+        Cursor* c = find_cursor(m);
+        if (!c) return;
+        be.free(c->mem);
+        held -= c->cost;
+        cursors.erase(cursors.begin() + (c - cursors.data()));
+    }
+    // the least recently touched cursor that read `now` does not touch (ties: the lower member), or nullptr
+    Cursor* oldest(uint64_t now) {
+        Cursor* best = nullptr;
+        for (Cursor& c : cursors)
+            if (c.touched < now && (!best || c.touched < best->touched)) best = &c;
+        return best;
+    }
+    // The budget for cursors in bytes; 0 = off (the default): every cursor is freed and a read is what it was without the cache.
+    // A smaller budget evicts least recently touched cursors until the rest fits.  One host wait the first time (the member
+    // offsets), none after.
+    void set_cache(uint64_t max_bytes) {
+        if (max_bytes) member_offsets();
+        budget = max_bytes;
+        while (held > budget) drop_cursor(oldest(reads + 1)->m);
+        last = RangeCacheStats{};
+    }
+    RangeCacheStats cache_stats() const {
+        RangeCacheStats c = last;
+        c.cursors = cursors.size(); c.bytes = held; c.budget = budget;
+        return c;
     }
 
     // Ranges [off[k], off[k] + len[k]) of the decoded data, written back to back in range order at d_dst.  dst_len = the sum of the
@@ -265,6 +333,7 @@ struct RangeReader {
             return;
         }
         const uint64_t M = ix.members;  // (sum > 0: the container has members)
+        if (budget) return read_cached(up, n_ranges, d_dst, sum, st, slots, t0);
         grow(d_ranges, ranges_cap, up.size(), false);
         be.h2d(d_ranges, up.data(), up.size() * 8);
         st.host_waits++;
@@ -327,6 +396,161 @@ struct RangeReader {
             st.decoded_bytes += h_produced[m];
         }
         st.total_s = be.now() - t0;
+    }
+
+    // A read with the cache on (the ranges are valid, sum > 0).  The policy, in ascending member order over the members the call
+    // touches: a cursor whose valid bytes cover the member's stop is a HIT (no decode); one that falls short is RESUMED; a member
+    // without a cursor gets a FRESH one if its cost fits the budget, after evicting least recently touched cursors that this call
+    // does not touch (ties: the lower member; nothing is evicted when even all of them would not make room); otherwise, or when
+    // the allocation fails, it is decoded into the transient arena and nothing is kept (UNCACHED).  A member whose decode fails
+    // loses its cursor.
+    void read_cached(std::vector<uint64_t>& up, size_t n_ranges, uint8_t* d_dst, uint64_t sum, RangeReadStats& st, uint32_t slots, double t0) {
+        const uint64_t M = ix.members, now = ++reads;
+        last = RangeCacheStats{};
+        // the plan: RangePlan on the host
+        std::vector<uint32_t> h_stop(M, 0), todo, tmembers;
+        for (size_t k = 0; k < n_ranges; k++) {
+            const uint64_t from = up[k], to = from + up[n_ranges + k];
+            if (to == from) continue;
+            for (uint64_t m = last_at_or_below(h_off.data(), M, from); m < M && h_off[m] < to; m++) {
+                const uint32_t ml = member_len(m);
+                if (!ml) continue;
+                const uint32_t s = (uint32_t)(std::min(to, h_off[m] + ml) - h_off[m]);
+                if (!h_stop[m]) tmembers.push_back((uint32_t)m);
+                h_stop[m] = std::max(h_stop[m], s);
+            }
+        }
+        std::sort(tmembers.begin(), tmembers.end());
+        for (uint32_t m : tmembers)
+            if (Cursor* c = find_cursor(m)) c->touched = now;
+        // addr | cursor | stop | list behind the ranges
+        const size_t r8 = up.size();
+        up.resize(r8 + 2 * M + M);  // (stop and list: M u32 each = M u64 together)
+        uint64_t* h_addr = up.data() + r8;
+        uint64_t* h_cur = h_addr + M;  // indexed as the list is
+        uint32_t* u_stop = (uint32_t*)(h_cur + M);
+        uint32_t* u_list = u_stop + M;
+        std::fill(h_addr, h_addr + 3 * M, 0);
+        std::vector<uint32_t> was(M, 0);      // valid bytes before this read, of a member that is decoded into a cursor
+        std::vector<uint8_t> kind(M, 0);      // 1 = decoded into a cursor, 2 = decoded into the arena
+        // a member's bytes lie in its cursor or in the arena: h_addr[m] is their address minus the container's, modulo 2^64, so that
+        // decoder and gather find them as `base + offset[m]` like every other caller's
+        const uint64_t base = (uint64_t)(uintptr_t)d_src;
+        uint64_t arena_bytes = 0;
+        for (uint32_t m : tmembers) {
+            Cursor* c = find_cursor(m);
+            if (c && c->produced >= h_stop[m]) {
+                last.hits++;
+                h_addr[m] = (uint64_t)(uintptr_t)c->mem - base;
+                continue;
+            }
+            if (c) last.resumed++;
+            else {
+                const uint64_t cost = cursor_cost(member_len(m));
+                uint64_t spare = 0;
+                for (const Cursor& o : cursors)
+                    if (o.touched < now) spare += o.cost;
+                if (cost <= budget && held - spare + cost <= budget) {
+                    while (held + cost > budget) {
+                        drop_cursor(oldest(now)->m);
+                        last.evicted++;
+                    }
+                    uint8_t* mem = nullptr;
+                    const size_t data = (size_t)(cost - cursor_state_bytes());
+                    try { mem = be.template alloc<uint8_t>((size_t)cost, false); } catch (const std::bad_alloc&) {} catch (const std::runtime_error&) {}
+                    if (mem) {
+                        be.memset(mem + data, 0, (size_t)cursor_state_bytes());  // a zeroed blob, as a transient slot's; a record that is not live
+                        auto at = std::lower_bound(cursors.begin(), cursors.end(), m, [](const Cursor& x, uint32_t y) { return x.m < y; });
+                        c = &*cursors.insert(at, Cursor{m, mem, cost, 0, now});
+                        held += cost;
+                        last.fresh++;
+                    }
+                }
+            }
+            if (c) {
+                kind[m] = 1;
+                was[m] = c->produced;
+                h_addr[m] = (uint64_t)(uintptr_t)c->mem - base;
+                h_cur[todo.size()] = (uint64_t)(uintptr_t)(c->mem + (c->cost - cursor_state_bytes()));
+            } else {
+                kind[m] = 2;
+                last.uncached++;
+                h_addr[m] = arena_bytes;  // (the arena may still move: its address is added below)
+                arena_bytes += ((uint64_t)h_stop[m] + 15) & ~(uint64_t)15;
+            }
+            u_list[todo.size()] = m;
+            todo.push_back(m);
+        }
+        std::copy(h_stop.begin(), h_stop.end(), u_stop);
+        const uint64_t need = todo.size();
+        if (slots == 0) slots = 1;
+        if (slots > need) slots = (uint32_t)need;
+        bool fresh = false;
+        if (last.uncached) {
+            grow(arena, arena_cap, (size_t)arena_bytes, false);
+            for (uint32_t m : todo)
+                if (kind[m] == 2) h_addr[m] += (uint64_t)(uintptr_t)arena - base;
+            fresh = state_slots < slots;
+            if (fresh) {
+                size_t cap = (size_t)state_slots * DecodeLayout::kBytes;
+                grow(state, cap, (size_t)slots * DecodeLayout::kBytes, true);
+                state_slots = slots;
+            }
+        }
+        grow(d_up, up_cap, up.size() * 8, false);
+        be.h2d(d_up, up.data(), up.size() * 8);
+        st.host_waits++;
+        const uint64_t *d_off = (const uint64_t*)d_up, *d_prefix = d_off + 2 * n_ranges, *d_addr = d_off + r8, *d_cur = d_addr + M;
+        const uint32_t *d_stop = (const uint32_t*)(d_cur + M), *d_list = d_stop + M;
+        be.memset(status(), 0, (size_t)M * 8);  // status (kDecOk = 0), produced
+        st.members_decoded = need;
+        be.set_timing(true);
+        uint64_t nl = 0, nby[4];
+        double msby[4];
+        be.collect_timed(&nl);
+        for (uint64_t first = 0; first < need; first += slots) {
+            const uint32_t count = need - first < slots ? (uint32_t)(need - first) : slots;
+            bool transient = false;
+            for (uint32_t k = 0; k < count; k++) transient |= kind[todo[first + k]] == 2;
+            if (transient && !fresh) be.memset(state, 0, (size_t)count * DecodeLayout::kBytes);  // (alloc zeroed a new one)
+            if (transient) fresh = false;
+            be.timed_begin(2);
+            DecodeArgs a{d_src, ix.begin, ix.end, d_addr, ix.out_len, const_cast<uint8_t*>(d_src), state, status(), (uint32_t)first, count};
+            a.list = d_list;
+            a.stop = d_stop;
+            a.produced = produced();
+            a.cursor = d_cur;
+            be.launch_waves(count, DecodeMemberCursor{a}, DecodeMemberCursor::lds_bytes());
+            be.timed_end(2);
+            st.launches++;
+        }
+        const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
+        be.timed_begin(1);
+        be.launch((size_t)RangeGather::units(sum, head),
+                  RangeGather{d_off, d_prefix, n_ranges, ix.out_off, d_addr, ix.out_len, status(), M, d_src, d_dst, sum, head});
+        be.timed_end(1);
+        std::vector<uint32_t> back((size_t)M * 2);
+        be.d2h(back.data(), status(), (size_t)M * 8);
+        st.host_waits++;
+        be.collect_timed(&nl, msby, nby);  // (the stream has drained: no further wait)
+        be.set_timing(false);
+        st.kernel_ms = msby[2];
+        st.gather_ms = msby[1];
+        const uint32_t *h_status = back.data(), *h_produced = h_status + M;
+        int64_t failed = -1;
+        for (uint32_t m : todo) {
+            if (h_status[m] != kDecOk) {
+                if (failed < 0) failed = m;
+                if (kind[m] == 1) drop_cursor(m);
+                continue;
+            }
+            st.decoded_bytes += h_produced[m] - was[m];
+            if (kind[m] == 1) find_cursor(m)->produced = h_produced[m];
+        }
+        st.total_s = be.now() - t0;
+        if (failed >= 0)
+            throw std::runtime_error(h_status[failed] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
+                                                                       : "invalid orz data (member " + std::to_string(failed) + ", status " + std::to_string(h_status[failed]) + ")");
     }
 };
 
