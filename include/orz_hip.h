@@ -202,6 +202,26 @@ int orz_members_encode(orz_members*, const void* src, size_t n, int src_on_devic
  * 1 for n = 0).  d_cap >= orz_stream_bound(member_bytes) * members always suffices; ORZ_ENOMEM when the buffer fills. */
 int orz_members_encode_to_device(orz_members*, const void* src, size_t n, int src_on_device, size_t member_bytes, uint8_t* d_dst,
                                  size_t d_cap, size_t* offs, size_t* lens, size_t* n_members_out);
+/* ONE MEMBER PER CALLER-GIVEN SEGMENT, in segment order: segment k is the seg_len[k] bytes at seg_src[k] (all host memory, or
+ * all on the workers' device when src_on_device != 0), for callers that hold a list of separate allocations of unequal sizes (the
+ * tensors of a checkpoint, the pages of a table) and want neither a packing copy nor a member boundary inside a tensor.  Any
+ * length: 0 (an empty member, as n == 0 gives above), below a block, several blocks; no alignment is asked of a pointer.  Member
+ * k's stream is byte for byte what orz_members_encode writes for that segment alone with member_bytes >= seg_len[k], whichever
+ * worker takes it and whatever that worker encoded before.  Workers, arenas and waits are those of the two calls above.
+ * orz_members_bound_segments: the sum of orz_stream_bound(seg_len[k]), a d_cap that always suffices.
+ * orz_members_encode_segments: the streams concatenated in segment order in host memory (*dst: release with orz_free);
+ *   lens (optional, n_segs entries) = each member's stream length.
+ * orz_members_encode_segments_to_device: the streams left in d_dst (d_cap bytes on the workers' one device) in whatever order
+ *   they finish; member k's stream is the lens[k] bytes at d_dst + offs[k] (host arrays of n_segs entries): the table
+ *   orz_decode_members_to_device, orz_decode_members_scatter and orz_reader_open take.
+ * n_segs == 0: ORZ_OK, no members, no bytes, nothing launched.  ORZ_EINVAL, before anything reaches the device: NULL arrays with
+ * n_segs > 0, a NULL segment of non-zero length, a device-resident segment that overlaps [d_dst, d_dst + d_cap), device-resident
+ * segments with workers on several devices.  ORZ_ENOMEM when d_dst fills up. */
+size_t orz_members_bound_segments(const size_t* seg_len, size_t n_segs);
+int orz_members_encode_segments(orz_members*, const void* const* seg_src, const size_t* seg_len, size_t n_segs, int src_on_device,
+                                uint8_t** dst, size_t* dst_len, size_t* lens);
+int orz_members_encode_segments_to_device(orz_members*, const void* const* seg_src, const size_t* seg_len, size_t n_segs,
+                                          int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens);
 /* decodes every stream of a concatenation (a plain single stream is the 1-member case) */
 int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len, size_t* n_members_out);
 
@@ -237,6 +257,29 @@ int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t*
 int orz_decode_members_to_device(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
                                  size_t n_members, uint8_t* d_dst, size_t d_cap, size_t* dst_len, size_t* n_members_out,
                                  size_t* out_offs, orz_decode_stats* stats);
+/* EACH MEMBER INTO A DESTINATION OF ITS OWN (orz_decode_scatter.h).  src / n / src_on_device / offs / lens / n_members exactly as
+ * for orz_decode_members_to_device.  Member k's decoded bytes go to d_dsts[k] (d_caps[k] bytes on `device`; host arrays of n_dsts
+ * entries); out_lens (optional, n_dsts entries) = each member's decoded size, filled also when the call fails with ORZ_ENOMEM;
+ * *n_members_out = members.  d_dsts == NULL only sizes: the first min(n_dsts, members) entries of out_lens are filled and nothing
+ * is decoded.  A member that decodes to 0 bytes may have any pointer and capacity 0.
+ *   ORZ_EINVAL, all found before any decode launch: malformed data and table entries as for orz_decode_members_to_device (the
+ *     first bad member is named); n_dsts different from the member count; a NULL destination of a member that has bytes; two
+ *     destinations of members that have bytes overlap (whole capacities count); a destination overlaps a device-resident src.
+ *   ORZ_ENOMEM naming the first member whose destination is smaller than its decoded size: NOTHING has been written to any
+ *     destination.
+ *   ORZ_EINVAL naming the member, after the launches: payload damage (the content of the destinations is then unspecified).
+ * Bytes identical to orz_decode_members_mem's, member by member.  Nothing outside [d_dsts[k], d_dsts[k] + out_lens[k]) is written
+ * for any k, and the output does not depend on what the buffers held.  The decode launches are those of
+ * orz_decode_members_to_device (ORZ_DECODE_SLOTS members in flight): this removes the copy that splits a concatenation, not
+ * decode time.  The host waits a constant number of times whatever the number of members: one read of the index record, one
+ * upload of destinations and capacities together, one read of the plan's record with the sizes, one read of the statuses -- 4,
+ * and one more each for the upload of a member table and of a host-resident src (6 at most); a sizing call: the index's waits
+ * and one read of the sizes.  orz_decode_members_scatter_host_waits: that count for the calling thread's last
+ * orz_decode_members_scatter call (orz_decode_stats is laid out as it always was). */
+int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                               size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, size_t n_dsts,
+                               size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_members_scatter_host_waits(void);
 
 /* ---- byte ranges of a members container (orz_decode_range.h) ------------------------------------------
  * A reader indexes a container ONCE (on the device, as orz_decode_members_to_device does) and then serves reads of byte

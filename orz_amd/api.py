@@ -270,6 +270,7 @@ class MemberEncoder:
         self.cfg = cfg_for_level(level)
         devs = [int(device)] if devices is None else [int(d) for d in devices]
         arr = (ctypes.c_int * len(devs))(*devs)
+        self._devices = devs
         self._h = self._lib.orz_members_new_multi(arr, len(devs), ctypes.byref(self.cfg), int(jobs))
         if not self._h:
             raise OrzError("orz_members_new_multi failed: " + _native.last_error())
@@ -308,6 +309,75 @@ class MemberEncoder:
                                                     ctypes.byref(got))
         _check(rc, "orz_members_encode_to_device")
         return [(offs[k], lens[k]) for k in range(got.value)]
+
+    def bound_segments(self, lengths):
+        """device bytes that always hold the members of segments of these lengths (orz_members_bound_segments)"""
+        n = len(lengths)
+        arr = (ctypes.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+        return int(self._lib.orz_members_bound_segments(arr, n))
+
+    @staticmethod
+    def _segment_arrays(ptrs, lengths):
+        n = len(ptrs)
+        return (ctypes.c_void_p * max(n, 1))(*[p or None for p in ptrs]), (ctypes.c_size_t * max(n, 1))(*lengths), n
+
+    def encode_segments(self, segments):
+        """One member per bytes-like object of `segments`, in that order (orz_members_encode_segments): no boundary falls inside
+        a segment and none is packed with another.  Returns (the members' streams concatenated, [each stream's length])."""
+        keep = [bytes(b) for b in segments]  # (no copy of what is `bytes` already; the library reads the objects' own buffers)
+        ptrs, lengths, n = self._segment_arrays([ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value if b else None for b in keep],
+                                                [len(b) for b in keep])
+        dst = ctypes.POINTER(ctypes.c_uint8)()
+        dlen = ctypes.c_size_t()
+        lens = (ctypes.c_size_t * max(n, 1))()
+        rc = self._lib.orz_members_encode_segments(self._h, ptrs, lengths, n, 0, ctypes.byref(dst), ctypes.byref(dlen), lens)
+        _check(rc, "orz_members_encode_segments")
+        del keep
+        try:
+            return ctypes.string_at(dst, dlen.value), [lens[k] for k in range(n)]
+        finally:
+            self._lib.orz_free(dst)
+
+    def encode_segments_to_device(self, seg_ptrs, seg_lens, dst_ptr, dst_cap, src_on_device=True):
+        """orz_members_encode_segments_to_device on raw addresses: segment k is the seg_lens[k] bytes at seg_ptrs[k]; returns
+        [(offset, length)] per member, in segment order, into the buffer at `dst_ptr`."""
+        ptrs, lengths, n = self._segment_arrays([int(p) for p in seg_ptrs], [int(x) for x in seg_lens])
+        offs, lens = (ctypes.c_size_t * max(n, 1))(), (ctypes.c_size_t * max(n, 1))()
+        rc = self._lib.orz_members_encode_segments_to_device(self._h, ptrs, lengths, n, 1 if src_on_device else 0,
+                                                             ctypes.c_void_p(int(dst_ptr)), int(dst_cap), offs, lens)
+        _check(rc, "orz_members_encode_segments_to_device")
+        return [(offs[k], lens[k]) for k in range(n)]
+
+    def encode_tensors(self, tensors, out=None):
+        """One member per tensor of `tensors` (contiguous, any dtype, encoded as their bytes; all on this encoder's GPU or all on
+        the CPU), left in device memory: returns (container, members).  `container`: a uint8 tensor on the GPU -- `out` when given,
+        else one of bound_segments() bytes trimmed to the furthest byte used; `members`: [(offset, length)] per tensor, what
+        MemberReader, decode_members_to_device and decode_members_into take as `members=`."""
+        import torch
+
+        if len(self._devices) != 1:
+            raise ValueError("device-resident output needs an encoder on one GPU")
+        dev = torch.device("cuda", self._devices[0])
+        tensors = list(tensors)
+        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
+            raise ValueError("tensors must be contiguous torch tensors")
+        on_dev = bool(tensors) and tensors[0].is_cuda
+        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
+            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
+        lengths = [t.numel() * t.element_size() for t in tensors]
+        if out is None:
+            out = torch.empty(self.bound_segments(lengths), dtype=torch.uint8, device=dev)
+            trim = True
+        else:
+            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
+            trim = False
+        if not tensors:
+            return (out[:0] if trim else out), []
+        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        members = self.encode_segments_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths,
+                                                 out.data_ptr(), out.numel(), src_on_device=on_dev)
+        return (out[: max(o + ln for o, ln in members)] if trim else out), members
 
     def close(self):
         if self._h:
@@ -412,6 +482,56 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
     if stats:
         res.append(st.as_dict())
     return tuple(res)
+
+
+def decode_members_into(src, outs, device=0, members=None, stats=False):
+    """decode members ON THE GPU, member k into the storage of `outs[k]` (orz_decode_members_scatter): no concatenation is made
+    and nothing is copied afterwards.  `src` and `members` as for decode_members_to_device; `outs`: contiguous tensors of any
+    dtype on cuda:`device`, one per member, each at least as large as its member (a member of no bytes takes an empty tensor).
+    Raises OrzError, with nothing written to any tensor, when a size does not fit, the count differs from the members' or two
+    tensors overlap.  Returns [decoded size of each member] (and the stats dict, with `host_waits`)."""
+    import torch
+
+    lib = _native.load()
+    dev = torch.device("cuda", int(device))
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError("src must be a contiguous uint8 tensor")
+        if src.is_cuda and src.device != dev:
+            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
+        keep, on_dev = src, src.is_cuda
+        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
+    else:
+        data = bytes(src)
+        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    outs = list(outs)
+    if any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in outs):
+        raise ValueError("outs must be contiguous tensors on %s" % dev)
+    if members is None:
+        offs = lens = None
+        nt = 0
+    else:
+        nt = len(members)
+        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
+        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
+    nd = len(outs)
+    caps = (ctypes.c_size_t * max(nd, 1))(*[t.numel() * t.element_size() for t in outs])
+    dsts = (ctypes.c_void_p * max(nd, 1))(*[(t.data_ptr() if t.numel() else None) for t in outs])
+    sizes = (ctypes.c_size_t * max(nd, 1))()
+    nm = ctypes.c_size_t()
+    st = _native.DecodeStats()
+    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+    rc = lib.orz_decode_members_scatter(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, nd, sizes, ctypes.byref(nm),
+                                        ctypes.byref(st))
+    _check(rc, "orz_decode_members_scatter")
+    del keep
+    res = [sizes[k] for k in range(nd)]
+    if stats:
+        d = st.as_dict()
+        d["host_waits"] = int(lib.orz_decode_members_scatter_host_waits())
+        return res, d
+    return res
 
 
 class MemberReader:

@@ -18,6 +18,7 @@
 #include "orz_decode_device.h"
 #include "orz_decode_index.h"
 #include "orz_decode_range.h"
+#include "orz_decode_scatter.h"
 #include "orz_host_decode.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
@@ -446,17 +447,28 @@ void orz_members_free(orz_members* m) {
 // wait: the next member's frame kernels queue behind the copy -- into the job's ARENA on that device at an offset drawn from an
 // atomic counter; `place[k]` says where member k lies.  Arena = the caller's buffer (orz_members_encode_to_device) or one the
 // members object owns; a member that does not fit an OWNED arena goes to host memory instead (incompressible input: the arena
-// is sized for ratio 0.5), into the caller's it fails the job.
+// is sized for ratio 0.5), into the caller's it fails the job.  What a worker encodes is a list of WORK ITEMS, one member each:
+// the cuts of one input every member_bytes (orz_members_encode) or the caller's own segments (orz_members_encode_segments).
 namespace {
+struct MemberItem { const uint8_t* p; size_t len; };
+// the work items of one contiguous input cut every member_bytes: one empty member for n == 0
+void member_cuts(const void* src, size_t n, size_t member_bytes, std::vector<MemberItem>& items) {
+    const size_t nm = n == 0 ? 1 : (n + member_bytes - 1) / member_bytes;
+    items.resize(nm);
+    for (size_t i = 0; i < nm; i++) {
+        const size_t off = i * member_bytes;
+        items[i] = MemberItem{(const uint8_t*)src + off, n == 0 ? 0 : std::min(member_bytes, n - off)};
+    }
+}
 struct MemberPlace { int device = -1; size_t off = 0, len = 0; std::vector<uint8_t> host; };
 struct MemberArena {
     int device; uint8_t* p; size_t cap; bool caller;
     std::atomic<size_t> used{0};
     MemberArena(int d, uint8_t* q, size_t c, bool cl) : device(d), p(q), cap(c), caller(cl) {}
 };
-int members_run(orz_members* m, const void* src, size_t n, int src_on_device, size_t member_bytes, std::vector<std::unique_ptr<MemberArena>>& arenas,
+int members_run(orz_members* m, const std::vector<MemberItem>& items, int src_on_device, std::vector<std::unique_ptr<MemberArena>>& arenas,
                 std::vector<MemberPlace>& place) {
-    const size_t nm = place.size();
+    const size_t nm = items.size();
     std::atomic<size_t> next{0};
     std::atomic<int> rc{ORZ_OK};
     std::string err;
@@ -466,22 +478,27 @@ int members_run(orz_members* m, const void* src, size_t n, int src_on_device, si
         return nullptr;
     };
     auto work = [&](orz_stream* s) {
+        bool copied = false;
         try {
             orz::HipBackend& be = *s->be;
             ORZ_HIP_CHECK(hipSetDevice(be.device()));  // every host thread talks to its worker's device
             MemberArena* ar = arena_of(be.device());
-            bool copied = false;
             for (;;) {
                 const size_t i = next.fetch_add(1);
                 if (i >= nm || rc.load() != ORZ_OK) break;
                 if (!s->enc) throw std::runtime_error("a worker has no encoder (a reconfiguration ran out of device memory)");
-                const size_t off = i * member_bytes, len = n == 0 ? 0 : std::min(member_bytes, n - off);
+                const uint8_t* const src = items[i].p;
+                const size_t len = items[i].len;
                 be.begin_encode();
-                const auto r = orz::encode_stream_device(*s->enc, be, (const uint8_t*)src + off, len, src_on_device != 0, nullptr, 0);
+                const auto r = orz::encode_stream_device(*s->enc, be, src, len, src_on_device != 0, nullptr, 0);
                 MemberPlace& pl = place[i];
                 pl.len = r.len;
-                const size_t at = ar ? ar->used.fetch_add(r.len) : 0;
-                if (ar && at + r.len <= ar->cap) {
+                // a place in the arena is taken only when the member fits it: one that does not leaves the counter as it was,
+                // so the smaller members behind it still land there
+                size_t at = ar ? ar->used.load() : 0;
+                bool fits = false;
+                while (ar && r.len <= ar->cap && at <= ar->cap - r.len && !(fits = ar->used.compare_exchange_weak(at, at + r.len))) {}
+                if (fits) {
                     pl.device = be.device(); pl.off = at;
                     be.select(3);
                     be.d2d(ar->p + at, r.data, r.len);
@@ -495,7 +512,7 @@ int members_run(orz_members* m, const void* src, size_t n, int src_on_device, si
                 if (verify) {
                     std::vector<uint8_t> h(r.len);
                     ORZ_HIP_CHECK(hipMemcpy(h.data(), r.data, r.len, hipMemcpyDeviceToHost));
-                    verify_stream_decode((const uint8_t*)src + off, len, src_on_device != 0, h.data(), h.size());
+                    verify_stream_decode(src, len, src_on_device != 0, h.data(), h.size());
                 }
             }
             if (copied) { be.select(3); be.sync(); be.select(0); }  // (the worker's moves into the arena: one wait per job)
@@ -503,6 +520,9 @@ int members_run(orz_members* m, const void* src, size_t n, int src_on_device, si
             int expect = ORZ_OK;
             const std::string msg = e.what();
             if (rc.compare_exchange_strong(expect, msg.find("output buffer is too small") != std::string::npos ? ORZ_ENOMEM : ORZ_ENODEV)) err = msg;
+            if (copied) {  // (a failed job returns the arena too: no move into it may still be under way)
+                try { s->be->select(3); s->be->sync(); s->be->select(0); } catch (const std::exception&) {}
+            }
         }
     };
     struct Joiner {  // joins whatever was started, also when starting a later thread throws
@@ -516,20 +536,19 @@ int members_run(orz_members* m, const void* src, size_t n, int src_on_device, si
     return ORZ_OK;
 }
 }  // namespace
-int orz_members_encode(orz_members* m, const void* src, size_t n, int src_on_device, size_t member_bytes, uint8_t** dst,
-                       size_t* dst_len, size_t* n_members_out) {
-    if (!m || !dst || !dst_len || (!src && n) || member_bytes == 0) return fail(ORZ_EINVAL, "bad argument");
-    if (src_on_device && m->workers.size() > 1) {
-        const int d0 = m->workers[0]->be->device();
-        for (orz_stream* w : m->workers)
-            if (w->be->device() != d0) return fail(ORZ_EINVAL, "device-resident input needs all workers on that device");
-    }
+namespace {
+bool one_device(const orz_members* m) {
+    const int d0 = m->workers[0]->be->device();
+    for (orz_stream* w : m->workers)
+        if (w->be->device() != d0) return false;
+    return true;
+}
+// The members of `items` gathered in host memory in item order (*dst: malloc'ed), by way of an arena per device the workers sit on,
+// owned by the members object and kept between calls, of `want` bytes at least.  lens (optional): each member's stream length.
+int members_encode_host(orz_members* m, const std::vector<MemberItem>& items, int src_on_device, size_t want, uint8_t** dst, size_t* dst_len,
+                        size_t* lens) {
     try {
-        const size_t nm = n == 0 ? 1 : (n + member_bytes - 1) / member_bytes;
-        // an arena per device the workers sit on, owned by the members object and kept between calls: sized for ratio 0.5 (text:
-        // 0.28) or the streams' bound, whichever is smaller
         std::vector<std::unique_ptr<MemberArena>> arenas;
-        const size_t want = std::min(nm * orz::stream_bound(std::min(member_bytes, n ? n : 1)), n / 2 + nm * 65536 + (32u << 20));
         for (orz_stream* w : m->workers) {
             const int dev = w->be->device();
             bool have = false;
@@ -549,8 +568,8 @@ int orz_members_encode(orz_members* m, const void* src, size_t n, int src_on_dev
                 arenas.push_back(std::move(a));
             }
         }
-        std::vector<MemberPlace> place(nm);
-        const int rc = members_run(m, src, n, src_on_device, member_bytes, arenas, place);
+        std::vector<MemberPlace> place(items.size());
+        const int rc = members_run(m, items, src_on_device, arenas, place);
         if (rc != ORZ_OK) return rc;
         // the members in input order: ONE copy each, from where it lies to its place in the result (round 6; before: device ->
         // a vector per member -> the result)
@@ -572,30 +591,113 @@ int orz_members_encode(orz_members* m, const void* src, size_t n, int src_on_dev
             }
             at += pl.len;
         }
+        if (lens)
+            for (size_t k = 0; k < place.size(); k++) lens[k] = place[k].len;
         *dst = p;
         *dst_len = total;
-        if (n_members_out) *n_members_out = nm;
         return ORZ_OK;
     } catch (const std::exception& e) {  // (allocation / thread start failures never cross the C boundary)
+        return fail(ORZ_ENOMEM, e.what());
+    }
+}
+// The members of `items` left in the caller's device buffer wherever they finish; offs / lens: where each lies.
+int members_encode_device(orz_members* m, const std::vector<MemberItem>& items, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs,
+                          size_t* lens) {
+    try {
+        std::vector<std::unique_ptr<MemberArena>> arenas;
+        arenas.emplace_back(new MemberArena(m->workers[0]->be->device(), d_dst, d_cap, true));
+        std::vector<MemberPlace> place(items.size());
+        const int rc = members_run(m, items, src_on_device, arenas, place);
+        if (rc != ORZ_OK) return rc;
+        for (size_t k = 0; k < place.size(); k++) { offs[k] = place[k].off; lens[k] = place[k].len; }
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    }
+}
+// the caller's segments as work items, or the reason they are refused
+const char* segment_items(const orz_members* m, const void* const* seg_src, const size_t* seg_len, size_t n_segs, int src_on_device,
+                          std::vector<MemberItem>& items) {
+    if (!m) return "null members object";
+    if (n_segs && (!seg_src || !seg_len)) return "null segment arrays";
+    for (size_t k = 0; k < n_segs; k++)
+        if (!seg_src[k] && seg_len[k]) return "a null segment of non-zero length";
+    if (src_on_device && n_segs && !one_device(m)) return "device-resident input needs all workers on that device";
+    items.resize(n_segs);
+    for (size_t k = 0; k < n_segs; k++) items[k] = MemberItem{(const uint8_t*)seg_src[k], seg_len[k]};
+    return nullptr;
+}
+}  // namespace
+int orz_members_encode(orz_members* m, const void* src, size_t n, int src_on_device, size_t member_bytes, uint8_t** dst,
+                       size_t* dst_len, size_t* n_members_out) {
+    if (!m || !dst || !dst_len || (!src && n) || member_bytes == 0) return fail(ORZ_EINVAL, "bad argument");
+    if (src_on_device && m->workers.size() > 1 && !one_device(m)) return fail(ORZ_EINVAL, "device-resident input needs all workers on that device");
+    try {
+        std::vector<MemberItem> items;
+        member_cuts(src, n, member_bytes, items);
+        const size_t nm = items.size();
+        // the arena: sized for ratio 0.5 (text: 0.28) or the streams' bound, whichever is smaller
+        const size_t want = std::min(nm * orz::stream_bound(std::min(member_bytes, n ? n : 1)), n / 2 + nm * 65536 + (32u << 20));
+        const int rc = members_encode_host(m, items, src_on_device, want, dst, dst_len, nullptr);
+        if (rc == ORZ_OK && n_members_out) *n_members_out = nm;
+        return rc;
+    } catch (const std::exception& e) {
         return fail(ORZ_ENOMEM, e.what());
     }
 }
 int orz_members_encode_to_device(orz_members* m, const void* src, size_t n, int src_on_device, size_t member_bytes, uint8_t* d_dst,
                                  size_t d_cap, size_t* offs, size_t* lens, size_t* n_members_out) {
     if (!m || !d_dst || !offs || !lens || (!src && n) || member_bytes == 0) return fail(ORZ_EINVAL, "bad argument");
-    const int d0 = m->workers[0]->be->device();
-    for (orz_stream* w : m->workers)
-        if (w->be->device() != d0) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
+    if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
     try {
-        const size_t nm = n == 0 ? 1 : (n + member_bytes - 1) / member_bytes;
-        std::vector<std::unique_ptr<MemberArena>> arenas;
-        arenas.emplace_back(new MemberArena(d0, d_dst, d_cap, true));
-        std::vector<MemberPlace> place(nm);
-        const int rc = members_run(m, src, n, src_on_device, member_bytes, arenas, place);
-        if (rc != ORZ_OK) return rc;
-        for (size_t k = 0; k < nm; k++) { offs[k] = place[k].off; lens[k] = place[k].len; }
-        if (n_members_out) *n_members_out = nm;
-        return ORZ_OK;
+        std::vector<MemberItem> items;
+        member_cuts(src, n, member_bytes, items);
+        const int rc = members_encode_device(m, items, src_on_device, d_dst, d_cap, offs, lens);
+        if (rc == ORZ_OK && n_members_out) *n_members_out = items.size();
+        return rc;
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    }
+}
+size_t orz_members_bound_segments(const size_t* seg_len, size_t n_segs) {
+    size_t total = 0;
+    for (size_t k = 0; seg_len && k < n_segs; k++) total += orz::stream_bound(seg_len[k]);
+    return total;
+}
+int orz_members_encode_segments(orz_members* m, const void* const* seg_src, const size_t* seg_len, size_t n_segs, int src_on_device,
+                                uint8_t** dst, size_t* dst_len, size_t* lens) {
+    if (!dst || !dst_len) return fail(ORZ_EINVAL, "bad argument");
+    try {
+        std::vector<MemberItem> items;
+        if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, items)) return fail(ORZ_EINVAL, why);
+        if (!n_segs) {  // no members, no bytes, nothing launched
+            uint8_t* p = (uint8_t*)std::malloc(1);
+            if (!p) return fail(ORZ_ENOMEM, "malloc failed");
+            *dst = p;
+            *dst_len = 0;
+            return ORZ_OK;
+        }
+        size_t in_total = 0;
+        for (const MemberItem& it : items) in_total += it.len;
+        const size_t want = std::min(orz_members_bound_segments(seg_len, n_segs), in_total / 2 + n_segs * 65536 + (32u << 20));
+        return members_encode_host(m, items, src_on_device, want, dst, dst_len, lens);
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    }
+}
+int orz_members_encode_segments_to_device(orz_members* m, const void* const* seg_src, const size_t* seg_len, size_t n_segs,
+                                          int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens) {
+    try {
+        std::vector<MemberItem> items;
+        if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, items)) return fail(ORZ_EINVAL, why);
+        if (!n_segs) return ORZ_OK;
+        if (!d_dst || !offs || !lens) return fail(ORZ_EINVAL, "bad argument");
+        if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
+        if (src_on_device)
+            for (size_t k = 0; k < n_segs; k++)
+                if (items[k].len && d_cap && items[k].p < d_dst + d_cap && d_dst < items[k].p + items[k].len)
+                    return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
+        return members_encode_device(m, items, src_on_device, d_dst, d_cap, offs, lens);
     } catch (const std::exception& e) {
         return fail(ORZ_ENOMEM, e.what());
     }
@@ -686,6 +788,38 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
         return fail(ORZ_EINVAL, e.what());
     }
 }
+
+thread_local uint64_t g_scatter_waits = 0;
+int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                               size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, size_t n_dsts, size_t* out_lens,
+                               size_t* n_members_out, orz_decode_stats* stats) {
+    g_scatter_waits = 0;
+    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps)) return fail(ORZ_EINVAL, "bad argument");
+    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    uint64_t members = 0;
+    orz::DecodeScatterStats st;
+    int rc = ORZ_OK;
+    try {
+        orz::HipBackend be(device);
+        orz::decode_members_scatter(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
+                                    (const uint64_t*)lens, n_members, d_dsts, (const uint64_t*)d_caps, n_dsts, (uint64_t*)out_lens, members, st,
+                                    env_u("ORZ_DECODE_SLOTS", 2048));
+    } catch (const orz::DecodeCapacityError& e) {
+        rc = fail(ORZ_ENOMEM, e.what());
+    } catch (const std::bad_alloc& e) {
+        rc = fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        rc = fail(ORZ_EINVAL, e.what());
+    }
+    g_scatter_waits = st.host_waits;
+    if (n_members_out) *n_members_out = (size_t)members;
+    if (stats && rc == ORZ_OK) {
+        stats->members = st.members; stats->in_bytes = st.in_bytes; stats->out_bytes = st.out_bytes;
+        stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
+    }
+    return rc;
+}
+uint64_t orz_decode_members_scatter_host_waits(void) { return g_scatter_waits; }
 
 // ------------------------------------------------------------------------------ byte ranges of a container
 struct orz_reader {

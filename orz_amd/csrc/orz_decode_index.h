@@ -26,7 +26,8 @@ enum : uint32_t {  // verdicts of the device index: one per message of index_mem
     kIxTooLong,       // a member of 4 GiB or more
     kIxTooDense,      // announces more output than its bits can code
     kIxTableRange,    // a table entry outside [0, n)
-    kIxTableEnd       // a table entry that does not end at its member's EOF byte
+    kIxTableEnd,      // a table entry that does not end at its member's EOF byte
+    kIxShortDestination  // (orz_decode_scatter.h) a member's own destination is smaller than the member
 };
 
 inline const char* index_message(uint32_t s) {
@@ -39,6 +40,7 @@ inline const char* index_message(uint32_t s) {
         case kIxTooDense: return "member announces more output than its bits can code: use the host decoder";
         case kIxTableRange: return "invalid orz data: member table entry out of range";
         case kIxTableEnd: return "invalid orz data: member table entry does not end at its member's EOF byte";
+        case kIxShortDestination: return "a member's destination is too small";
         default: return "invalid orz data: unknown index verdict";
     }
 }

@@ -1,0 +1,218 @@
+// orz_decode_scatter.h -- members decoded each into a DESTINATION OF ITS OWN: the list-of-buffers twin of decode_members_to_device.
+//
+// decode_members_to_device (orz_decode_index.h) lays the members' bytes end to end in one buffer.  Here member k's bytes go to
+// d_dsts[k], a device buffer of d_caps[k] bytes the caller owns (the tensors of a checkpoint, the pages of a table).  Nothing new
+// decodes: the index is DeviceIndex's, the decode launches are DecodeMember's, and the only thing that changes is out_off[m], which
+// DecodeArgs already allows to be "the member's address minus `out`, modulo 2^64".  ScatterPlan writes those offsets on the
+// device, from ONE upload of the destinations, and holds each capacity against the size the index found; ScatterVerdict reduces
+// the verdicts to the first short destination, so the host learns in one read whether it may launch.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "orz_decode_index.h"
+
+namespace orz {
+
+struct ScatterRecord {  // what the host reads back of a plan: one record, behind the sizes
+    uint64_t members;
+    uint64_t bad;     // first member whose destination is short (members when there is none)
+    uint32_t status;  // kIxOk or kIxShortDestination
+    uint32_t pad;
+};
+
+// One lane per member: where the member's bytes go, as an offset from `base` modulo 2^64 (base + out_off[m] == dsts[m] in 64-bit
+// arithmetic, whichever of the two is the higher address), the verdict on its capacity, and its size next to the record for the
+// host's one read.  A member of no bytes is never short and its offset is never used.
+struct ScatterPlan {
+    const uint64_t* dsts;     // [members] the destinations' addresses
+    const uint64_t* caps;     // [members] their capacities
+    const uint32_t* out_len;  // [members] the index's sizes
+    uint64_t base;
+    uint64_t* out_off;
+    uint32_t* verdict;
+    uint32_t* sizes;
+    uint64_t members;
+    ORZ_HD void operator()(size_t m) const {
+        if (m >= members) return;
+        const uint32_t len = out_len[m];
+        out_off[m] = dsts[m] - base;
+        verdict[m] = caps[m] < len ? (uint32_t)kIxShortDestination : (uint32_t)kIxOk;
+        sizes[m] = len;
+    }
+};
+
+// One wavefront: the first member whose verdict is not kIxOk, by ballot over 64 members at a time (IndexScan's search).  A launch
+// of its own: it reads what ScatterPlan's launch wrote.
+struct ScatterVerdict {
+    const uint32_t* verdict;
+    uint64_t members;
+    ScatterRecord* rec;
+    static size_t lds_bytes() { return 0; }
+    template <class W>
+    ORZ_D void operator()(W& w) const {
+        const uint32_t lane = w.lane();
+        uint64_t bad = members;
+        uint32_t why = kIxOk;
+        for (uint64_t at = 0; at < members; at += 64) {
+            const uint64_t k = at + lane;
+            const uint32_t s = k < members ? verdict[k] : (uint32_t)kIxOk;
+            const uint64_t bm = w.ballot(s != kIxOk);
+            const uint32_t lead = bm ? (uint32_t)__builtin_ctzll(bm) : 0;
+            const uint32_t s_lead = w.shfl(s, lead);
+            if (bm) {  // (wave-uniform)
+                bad = at + lead;
+                why = s_lead;
+                break;
+            }
+        }
+        if (lane == 0) *rec = ScatterRecord{members, bad, why, 0};
+    }
+};
+
+struct DecodeScatterStats : DecodeStats {
+    uint64_t host_waits = 0;
+};
+
+// Decodes the members of `src` (n / src_on_device / table / offs / lens / n_table as for decode_members_to_device), member k into
+// the d_caps[k] bytes of device memory at d_dsts[k] (host arrays of n_dsts entries).  d_dsts == nullptr sizes only: out_lens
+// receives the first min(n_dsts, members) decoded sizes and nothing is decoded.  Otherwise out_lens (when not null) receives all
+// n_dsts of them, also when the call fails for a short destination.  Sets `members`.
+// Throws, all before any decode launch and so before a byte of any destination is written:
+//   std::runtime_error      malformed data (the index's message, naming the first bad member); n_dsts != members; a null
+//                           destination of a member that has bytes; two destinations of members that have bytes overlap (their
+//                           whole capacities count); a destination overlaps a device-resident container
+//   DecodeCapacityError     a destination smaller than its member, naming the first such member
+// and std::runtime_error naming the member after the launches when a member's payload is damaged.
+// Host waits (stats.host_waits), a constant whatever the number of members: the upload of a host container and of a table as
+// uploads always were, ONE read of the index record, ONE upload of destinations and capacities, ONE read of the plan's record
+// with the sizes, ONE read of the statuses after the decode launches: 4, 5 with a table or a host container, 6 with both.  A
+// sizing call: the index's waits and one read of the sizes.
+template <class BE>
+void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_device, bool table, const uint64_t* offs,
+                            const uint64_t* lens, size_t n_table, uint8_t* const* d_dsts, const uint64_t* d_caps, size_t n_dsts,
+                            uint64_t* out_lens, uint64_t& members, DecodeScatterStats& stats, uint32_t slots = 2048) {
+    const double t0 = be.now();
+    const bool sizing = d_dsts == nullptr;
+    if (!sizing && n_dsts && !d_caps) throw std::runtime_error("invalid argument: destinations without capacities");
+    struct Owned {  // the uploaded container, the plan and the decoder's state, freed on every way out
+        BE& be;
+        void* p[3] = {nullptr, nullptr, nullptr};
+        ~Owned() { for (void* q : p) if (q) be.free(q); }
+    } own{be};
+    const uint8_t* d_src = src;
+    if (!src_on_device) {
+        uint8_t* up = be.template alloc<uint8_t>(n, false);
+        own.p[0] = up;
+        be.h2d(up, src, n);
+        stats.host_waits++;
+        d_src = up;
+    }
+    DeviceIndex<BE> ix(be);
+    ix.build(d_src, n, table, offs, lens, n_table, true);
+    stats.host_waits += ix.host_waits;
+    const uint64_t M = ix.members;
+    members = M;
+    stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
+    if (sizing) {
+        const uint64_t k = std::min<uint64_t>(M, out_lens ? n_dsts : 0);
+        if (k) {
+            std::vector<uint32_t> back((size_t)k);
+            be.d2h(back.data(), ix.out_len, (size_t)k * 4);
+            stats.host_waits++;
+            std::copy(back.begin(), back.end(), out_lens);
+        }
+        stats.total_s = be.now() - t0;
+        return;
+    }
+    if (n_dsts != M)
+        throw std::runtime_error("invalid argument: " + std::to_string(n_dsts) + " destinations for " + std::to_string(M) + " members");
+    if (!M) {
+        stats.total_s = be.now() - t0;
+        return;
+    }
+    // the plan's memory: dsts | caps (u64, ONE upload) | verdict | sizes (u32) | record, sizes and record read back together
+    const size_t rec_at = ((size_t)M * 24 + 7) / 8 * 8;
+    uint8_t* plan = be.template alloc<uint8_t>(rec_at + sizeof(ScatterRecord), false);
+    own.p[1] = plan;
+    uint64_t* p_dsts = (uint64_t*)plan;
+    uint64_t* p_caps = p_dsts + M;
+    uint32_t* p_verdict = (uint32_t*)(p_caps + M);
+    uint32_t* p_sizes = p_verdict + M;
+    uint64_t base = 0;
+    {
+        std::vector<uint64_t> up((size_t)M * 2);
+        for (uint64_t m = 0; m < M; m++) {
+            up[m] = (uint64_t)(uintptr_t)d_dsts[m];
+            up[M + m] = d_caps[m];
+            if (!base) base = up[m];
+        }
+        be.h2d(p_dsts, up.data(), (size_t)M * 16);
+        stats.host_waits++;
+    }
+    uint8_t* const out = (uint8_t*)(uintptr_t)base;
+    be.launch(M, ScatterPlan{p_dsts, p_caps, ix.out_len, base, ix.out_off, p_verdict, p_sizes, M});
+    be.launch_waves(1, ScatterVerdict{p_verdict, M, (ScatterRecord*)(plan + rec_at)}, ScatterVerdict::lds_bytes());
+    std::vector<uint8_t> back(rec_at + sizeof(ScatterRecord) - (size_t)M * 20);
+    be.d2h(back.data(), (const uint8_t*)p_sizes, back.size());
+    stats.host_waits++;
+    const uint32_t* sizes = (const uint32_t*)back.data();
+    ScatterRecord rec;
+    std::memcpy(&rec, back.data() + (rec_at - (size_t)M * 20), sizeof rec);
+    if (out_lens) std::copy(sizes, sizes + M, out_lens);
+    // the destinations of members that have bytes, by address: none null, none inside another, none inside the container
+    std::vector<std::pair<uint64_t, uint64_t>> iv;  // (address, member)
+    for (uint64_t m = 0; m < M; m++) {
+        if (!sizes[m]) continue;
+        if (!d_dsts[m]) throw std::runtime_error("invalid argument: no destination for member " + std::to_string(m));
+        iv.emplace_back((uint64_t)(uintptr_t)d_dsts[m], m);
+    }
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 0; i < iv.size(); i++) {
+        const uint64_t a = iv[i].first, m = iv[i].second, cap = d_caps[m];
+        if (cap > ~a) throw std::runtime_error("invalid argument: the destination of member " + std::to_string(m) + " wraps the address space");
+        if (i + 1 < iv.size() && iv[i + 1].first < a + cap)
+            throw std::runtime_error("invalid argument: the destinations of members " + std::to_string(std::min(m, iv[i + 1].second)) + " and " +
+                                     std::to_string(std::max(m, iv[i + 1].second)) + " overlap");
+        const uint64_t s = (uint64_t)(uintptr_t)src;
+        if (src_on_device && n && cap && a < s + n && s < a + cap)
+            throw std::runtime_error("invalid argument: the container and the destination of member " + std::to_string(m) + " overlap");
+    }
+    if (rec.status != kIxOk)
+        throw DecodeCapacityError("the destination of member " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) +
+                                  " bytes, too small for " + std::to_string(sizes[rec.bad]));
+    uint64_t nl = 0, nby[4];
+    double msby[4];
+    if (slots == 0) slots = 1;
+    if (slots > M) slots = (uint32_t)M;
+    uint8_t* d_state = be.template alloc<uint8_t>((size_t)slots * DecodeLayout::kBytes);
+    own.p[2] = d_state;
+    be.set_timing(true);
+    be.collect_timed(&nl);
+    for (uint64_t first = 0; first < M; first += slots) {
+        const uint32_t count = M - first < slots ? (uint32_t)(M - first) : slots;
+        if (first) be.memset(d_state, 0, (size_t)slots * DecodeLayout::kBytes);  // (alloc zeroes the first round)
+        be.timed_begin(2);
+        be.launch_waves(count, DecodeMember{DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, out, d_state, ix.status,
+                                                       (uint32_t)first, count}}, DecodeMember::lds_bytes());
+        be.timed_end(2);
+        stats.launches++;
+    }
+    be.collect_timed(&nl, msby, nby);
+    stats.kernel_ms = msby[2];
+    be.set_timing(false);
+    std::vector<uint32_t> status((size_t)M);
+    be.d2h(status.data(), ix.status, (size_t)M * 4);
+    stats.host_waits++;
+    for (uint64_t m = 0; m < M; m++)
+        if (status[m] != kDecOk)
+            throw std::runtime_error(status[m] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
+                                                                : "invalid orz data (member " + std::to_string(m) + ", status " + std::to_string(status[m]) + ")");
+    stats.total_s = be.now() - t0;
+}
+
+}  // namespace orz
