@@ -56,6 +56,30 @@ unsigned env_u(const char* name, unsigned dflt) {
     return v && *v ? (unsigned)std::strtoul(v, nullptr, 10) : dflt;
 }
 
+// ---- shared by the decode entry points
+unsigned decode_slots() { return env_u("ORZ_DECODE_SLOTS", 2048); }  // members in flight at once
+bool device_ok(int device) { return device >= 0 && device < orz_device_count(); }
+void put_stats(orz_decode_stats* out, const orz::DecodeStats& st) {
+    if (!out) return;
+    out->members = st.members; out->in_bytes = st.in_bytes; out->out_bytes = st.out_bytes;
+    out->launches = st.launches; out->kernel_ms = st.kernel_ms; out->total_s = st.total_s;
+}
+// Runs f.  What it throws becomes the thread's message and ORZ_ENOMEM (a buffer of the caller's that is too small, memory that
+// ran out) or ORZ_EINVAL (anything else).
+template <class F>
+int mapped(F&& f) {
+    try {
+        f();
+        return ORZ_OK;
+    } catch (const orz::DecodeCapacityError& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    } catch (const std::bad_alloc& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        return fail(ORZ_EINVAL, e.what());
+    }
+}
+
 using Enc = orz::StreamEncoder<orz::HipBackend>;
 
 // parse mode of a new encoder: the GPU-native fast mode unless ORZ_MODE=exact asks for the reference-identical parse
@@ -735,22 +759,19 @@ int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* 
 int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len,
                               size_t* n_members_out, orz_decode_stats* stats) {
     if ((!src && n) || !dst || !dst_len) return fail(ORZ_EINVAL, "bad argument");
-    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
     try {
         orz::HipBackend be(device);
         std::vector<uint8_t> out;
         orz::DecodeStats st;
-        orz::decode_members_device(be, src, n, out, st, env_u("ORZ_DECODE_SLOTS", 2048));
+        orz::decode_members_device(be, src, n, out, st, decode_slots());
         uint8_t* p = (uint8_t*)std::malloc(out.size() ? out.size() : 1);
         if (!p) return fail(ORZ_ENOMEM, "malloc failed");
         std::memcpy(p, out.data(), out.size());
         *dst = p;
         *dst_len = out.size();
         if (n_members_out) *n_members_out = (size_t)st.members;
-        if (stats) {
-            stats->members = st.members; stats->in_bytes = st.in_bytes; stats->out_bytes = st.out_bytes;
-            stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
-        }
+        put_stats(stats, st);
         return ORZ_OK;
     } catch (const std::exception& e) {
         return fail(ORZ_EINVAL, e.what());
@@ -762,31 +783,27 @@ int orz_decode_members_to_device(int device, const void* src, size_t n, int src_
                                  size_t* out_offs, orz_decode_stats* stats) {
     if ((!src && n) || !dst_len || (!d_dst && d_cap) || (!offs != !lens))
         return fail(ORZ_EINVAL, "bad argument");
-    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
     static_assert(sizeof(size_t) == sizeof(uint64_t), "the member table is handed to the device as 64-bit words");
     uint64_t total = 0, members = 0;
-    try {
+    const auto sizes_out = [&] {
+        *dst_len = (size_t)total;
+        if (n_members_out) *n_members_out = (size_t)members;
+    };
+    return mapped([&] {
         orz::HipBackend be(device);
         orz::DecodeToDeviceStats st;
-        orz::decode_members_to_device(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
-                                      (const uint64_t*)lens, n_members, d_dst, d_cap, total, members, (uint64_t*)out_offs, st,
-                                      env_u("ORZ_DECODE_SLOTS", 2048));
-        *dst_len = (size_t)total;
-        if (n_members_out) *n_members_out = (size_t)members;
-        if (stats) {
-            stats->members = st.members; stats->in_bytes = st.in_bytes; stats->out_bytes = st.out_bytes;
-            stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
+        try {
+            orz::decode_members_to_device(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
+                                          (const uint64_t*)lens, n_members, d_dst, d_cap, total, members, (uint64_t*)out_offs, st,
+                                          decode_slots());
+        } catch (const orz::DecodeCapacityError&) {  // (the size is known: reported as the sizing call reports it)
+            sizes_out();
+            throw;
         }
-        return ORZ_OK;
-    } catch (const orz::DecodeCapacityError& e) {  // (the size is known: reported as the sizing call reports it)
-        *dst_len = (size_t)total;
-        if (n_members_out) *n_members_out = (size_t)members;
-        return fail(ORZ_ENOMEM, e.what());
-    } catch (const std::bad_alloc& e) {
-        return fail(ORZ_ENOMEM, e.what());
-    } catch (const std::exception& e) {
-        return fail(ORZ_EINVAL, e.what());
-    }
+        sizes_out();
+        put_stats(stats, st);
+    });
 }
 
 thread_local uint64_t g_scatter_waits = 0;
@@ -795,28 +812,18 @@ int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on
                                size_t* n_members_out, orz_decode_stats* stats) {
     g_scatter_waits = 0;
     if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps)) return fail(ORZ_EINVAL, "bad argument");
-    if (device < 0 || device >= orz_device_count()) return fail(ORZ_ENODEV, "no such HIP device");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
     uint64_t members = 0;
     orz::DecodeScatterStats st;
-    int rc = ORZ_OK;
-    try {
+    const int rc = mapped([&] {
         orz::HipBackend be(device);
         orz::decode_members_scatter(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
                                     (const uint64_t*)lens, n_members, d_dsts, (const uint64_t*)d_caps, n_dsts, (uint64_t*)out_lens, members, st,
-                                    env_u("ORZ_DECODE_SLOTS", 2048));
-    } catch (const orz::DecodeCapacityError& e) {
-        rc = fail(ORZ_ENOMEM, e.what());
-    } catch (const std::bad_alloc& e) {
-        rc = fail(ORZ_ENOMEM, e.what());
-    } catch (const std::exception& e) {
-        rc = fail(ORZ_EINVAL, e.what());
-    }
+                                    decode_slots());
+    });
     g_scatter_waits = st.host_waits;
     if (n_members_out) *n_members_out = (size_t)members;
-    if (stats && rc == ORZ_OK) {
-        stats->members = st.members; stats->in_bytes = st.in_bytes; stats->out_bytes = st.out_bytes;
-        stats->launches = st.launches; stats->kernel_ms = st.kernel_ms; stats->total_s = st.total_s;
-    }
+    if (rc == ORZ_OK) put_stats(stats, st);
     return rc;
 }
 uint64_t orz_decode_members_scatter_host_waits(void) { return g_scatter_waits; }
@@ -830,19 +837,15 @@ struct orz_reader {
 orz_reader* orz_reader_open(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
                             size_t n_members) {
     if ((!src && n) || (!offs != !lens)) { fail(ORZ_EINVAL, "bad argument"); return nullptr; }
-    if (device < 0 || device >= orz_device_count()) { fail(ORZ_ENODEV, "no such HIP device"); return nullptr; }
-    try {
-        std::unique_ptr<orz_reader> r(new orz_reader);
+    if (!device_ok(device)) { fail(ORZ_ENODEV, "no such HIP device"); return nullptr; }
+    std::unique_ptr<orz_reader> r;
+    const int rc = mapped([&] {
+        r.reset(new orz_reader);
         r->be.reset(new orz::HipBackend(device));
         r->rd.reset(new orz::RangeReader<orz::HipBackend>(*r->be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr,
                                                           (const uint64_t*)offs, (const uint64_t*)lens, n_members));
-        return r.release();
-    } catch (const std::bad_alloc& e) {
-        fail(ORZ_ENOMEM, e.what());
-    } catch (const std::exception& e) {
-        fail(ORZ_EINVAL, e.what());
-    }
-    return nullptr;
+    });
+    return rc == ORZ_OK ? r.release() : nullptr;
 }
 
 void orz_reader_close(orz_reader* r) { delete r; }
@@ -867,16 +870,7 @@ int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, siz
     if (!r || !dst_len) return fail(ORZ_EINVAL, "bad argument");
     orz::RangeReadStats st;
     uint64_t total = 0;
-    int rc = ORZ_OK;
-    try {
-        r->rd->read(off, len, n_ranges, d_dst, d_cap, total, st, env_u("ORZ_DECODE_SLOTS", 2048));
-    } catch (const orz::DecodeCapacityError& e) {
-        rc = fail(ORZ_ENOMEM, e.what());
-    } catch (const std::bad_alloc& e) {
-        rc = fail(ORZ_ENOMEM, e.what());
-    } catch (const std::exception& e) {
-        rc = fail(ORZ_EINVAL, e.what());
-    }
+    const int rc = mapped([&] { r->rd->read(off, len, n_ranges, d_dst, d_cap, total, st, decode_slots()); });
     *dst_len = total;
     if (stats) {
         stats->ranges = st.ranges; stats->members_decoded = st.members_decoded; stats->decoded_bytes = st.decoded_bytes;
@@ -888,14 +882,7 @@ int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, siz
 
 int orz_reader_set_cache(orz_reader* r, uint64_t max_bytes) {
     if (!r) return fail(ORZ_EINVAL, "bad argument");
-    try {
-        r->rd->set_cache(max_bytes);
-        return ORZ_OK;
-    } catch (const std::bad_alloc& e) {
-        return fail(ORZ_ENOMEM, e.what());
-    } catch (const std::exception& e) {
-        return fail(ORZ_EINVAL, e.what());
-    }
+    return mapped([&] { r->rd->set_cache(max_bytes); });
 }
 
 uint64_t orz_reader_cursor_state_bytes(void) { return orz::RangeReader<orz::HipBackend>::cursor_state_bytes(); }

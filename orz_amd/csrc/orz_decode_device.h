@@ -607,6 +607,12 @@ inline MemberIndex index_members(const uint8_t* src, size_t n) {
     return ix;
 }
 
+}  // namespace orz
+
+#include "orz_decode_drive.h"  // (below the types it drives)
+
+namespace orz {
+
 // Decodes every member of the container on the backend's device; `slots` members are in flight at once
 // (one wavefront and one 7.3 MB state blob each).
 template <class BE>
@@ -618,45 +624,28 @@ void decode_members_device(BE& be, const uint8_t* src, size_t n, std::vector<uin
     out.assign(ix.out_total, 0);
     stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.out_total;
     if (M == 0) { stats.total_s = be.now() - t0; return; }
-    if (slots > M) slots = M;
-    uint8_t* d_src = be.template alloc<uint8_t>(n);
-    uint8_t* d_out = be.template alloc<uint8_t>(ix.out_total);
-    uint64_t* d_begin = be.template alloc<uint64_t>(M);
-    uint64_t* d_end = be.template alloc<uint64_t>(M);
-    uint64_t* d_off = be.template alloc<uint64_t>(M);
-    uint32_t* d_len = be.template alloc<uint32_t>(M);
-    uint32_t* d_status = be.template alloc<uint32_t>(M);
-    uint8_t* d_state = be.template alloc<uint8_t>((size_t)slots * DecodeLayout::kBytes);
-    be.h2d(d_src, src, n);
-    be.h2d(d_begin, ix.begin.data(), (size_t)M * 8);
-    be.h2d(d_end, ix.end.data(), (size_t)M * 8);
-    be.h2d(d_off, ix.out_off.data(), (size_t)M * 8);
-    be.h2d(d_len, ix.out_len.data(), (size_t)M * 4);
-    be.set_timing(true);
-    uint64_t dummy = 0;
-    be.collect_timed(&dummy);
-    for (uint32_t first = 0; first < M; first += slots) {
-        const uint32_t count = M - first < slots ? M - first : slots;
-        if (first) be.memset(d_state, 0, (size_t)slots * DecodeLayout::kBytes);  // (alloc zeroes the first round)
-        be.timed_begin(2);  // (a slot that is recorded without profile mode)
-        be.launch_waves(count, DecodeMember{DecodeArgs{d_src, d_begin, d_end, d_off, d_len, d_out, d_state, d_status, first, count}}, DecodeMember::lds_bytes());
-        be.timed_end(2);
-        stats.launches++;
-    }
-    uint64_t nl = 0, nby[4];
-    double msby[4];
-    be.collect_timed(&nl, msby, nby);
-    stats.kernel_ms = msby[2];
-    be.set_timing(false);
     std::vector<uint32_t> status(M);
-    be.d2h(status.data(), d_status, (size_t)M * 4);
-    be.d2h(out.data(), d_out, ix.out_total);
-    for (void* p : {(void*)d_src, (void*)d_out, (void*)d_begin, (void*)d_end, (void*)d_off, (void*)d_len, (void*)d_status, (void*)d_state}) be.free(p);
+    {
+        DeviceBuffers<BE> own(be);
+        uint8_t* d_src = own.template alloc<uint8_t>(n);
+        uint8_t* d_out = own.template alloc<uint8_t>(ix.out_total);
+        uint64_t* d_begin = own.template alloc<uint64_t>(M);
+        uint64_t* d_end = own.template alloc<uint64_t>(M);
+        uint64_t* d_off = own.template alloc<uint64_t>(M);
+        uint32_t* d_len = own.template alloc<uint32_t>(M);
+        uint32_t* d_status = own.template alloc<uint32_t>(M);
+        uint8_t* d_state = own.template alloc<uint8_t>((size_t)clamp_slots(M, slots) * DecodeLayout::kBytes);
+        be.h2d(d_src, src, n);
+        be.h2d(d_begin, ix.begin.data(), (size_t)M * 8);
+        be.h2d(d_end, ix.end.data(), (size_t)M * 8);
+        be.h2d(d_off, ix.out_off.data(), (size_t)M * 8);
+        be.h2d(d_len, ix.out_len.data(), (size_t)M * 4);
+        decode_all(be, DecodeArgs{d_src, d_begin, d_end, d_off, d_len, d_out, d_state, d_status, 0, 0}, M, slots, own, stats);
+        be.d2h(status.data(), d_status, (size_t)M * 4);
+        be.d2h(out.data(), d_out, ix.out_total);
+    }  // (the buffers go here: their release counts into total_s, as it always did)
     for (uint32_t m = 0; m < M; m++)
-        if (status[m] != kDecOk)
-            throw std::runtime_error(status[m] == kDecTooLarge ? "member larger than one block: use the host decoder"
-                                     : status[m] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
-                                                               : "invalid orz data (member " + std::to_string(m) + ", status " + std::to_string(status[m]) + ")");
+        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
     stats.total_s = be.now() - t0;
 }
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "orz_decode_device.h"
+#include "orz_decode_drive.h"
 
 namespace orz {
 
@@ -285,19 +286,8 @@ void decode_members_to_device(BE& be, const uint8_t* src, size_t n, bool src_on_
     const bool sizing = d_dst == nullptr && d_cap == 0;
     if (src_on_device && n && d_cap && (const uint8_t*)d_dst < src + n && src < (const uint8_t*)d_dst + d_cap)
         throw std::runtime_error("invalid argument: the container and the output buffer overlap");
-    struct Owned {  // the uploaded container and the decoder's state, freed on every way out
-        BE& be;
-        void* p[2] = {nullptr, nullptr};
-        ~Owned() { for (void* q : p) if (q) be.free(q); }
-    } own{be};
-    const uint8_t* d_src = src;
-    if (!src_on_device) {
-        uint8_t* up = be.template alloc<uint8_t>(n, false);
-        own.p[0] = up;
-        be.h2d(up, src, n);
-        stats.host_waits++;
-        d_src = up;
-    }
+    DeviceBuffers<BE> own(be);  // the uploaded container and the decoder's state
+    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
     DeviceIndex<BE> ix(be);
     ix.build(d_src, n, table, offs, lens, n_table, !sizing || out_offs != nullptr);
     stats.host_waits += ix.host_waits;
@@ -307,28 +297,8 @@ void decode_members_to_device(BE& be, const uint8_t* src, size_t n, bool src_on_
     stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
     if (!sizing && d_cap < ix.total)
         throw DecodeCapacityError("output buffer of " + std::to_string(d_cap) + " bytes is too small for " + std::to_string(ix.total));
-    uint64_t nl = 0, nby[4];
-    double msby[4];
-    if (!sizing && M) {
-        if (slots == 0) slots = 1;
-        if (slots > M) slots = (uint32_t)M;
-        uint8_t* d_state = be.template alloc<uint8_t>((size_t)slots * DecodeLayout::kBytes);
-        own.p[1] = d_state;
-        be.set_timing(true);
-        be.collect_timed(&nl);
-        for (uint64_t first = 0; first < M; first += slots) {
-            const uint32_t count = M - first < slots ? (uint32_t)(M - first) : slots;
-            if (first) be.memset(d_state, 0, (size_t)slots * DecodeLayout::kBytes);  // (alloc zeroes the first round)
-            be.timed_begin(2);
-            be.launch_waves(count, DecodeMember{DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, d_dst, d_state, ix.status,
-                                                           (uint32_t)first, count}}, DecodeMember::lds_bytes());
-            be.timed_end(2);
-            stats.launches++;
-        }
-        be.collect_timed(&nl, msby, nby);
-        stats.kernel_ms = msby[2];
-        be.set_timing(false);
-    }
+    if (!sizing && M)
+        decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, d_dst, nullptr, ix.status, 0, 0}, M, slots, own, stats);
     const bool want_status = !sizing && M;
     if (want_status || (out_offs && M)) {
         // out_off and status lie side by side: one read for either or both
@@ -340,9 +310,7 @@ void decode_members_to_device(BE& be, const uint8_t* src, size_t n, bool src_on_
         if (want_status) {
             const uint32_t* status = (const uint32_t*)(back.data() + (size_t)M * 8);
             for (uint64_t m = 0; m < M; m++)
-                if (status[m] != kDecOk)
-                    throw std::runtime_error(status[m] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
-                                                                        : "invalid orz data (member " + std::to_string(m) + ", status " + std::to_string(status[m]) + ")");
+                if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
         }
     }
     stats.total_s = be.now() - t0;

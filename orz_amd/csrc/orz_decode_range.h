@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "orz_decode_index.h"
+#include "orz_decode_drive.h"
 #include "orz_kernels.h"  // (ORZ_ATOMIC_MAX)
 
 namespace orz {
@@ -346,8 +347,7 @@ struct RangeReader {
         st.host_waits++;
         if (r.needed == 0 || r.needed > M || r.scratch_bytes < 16 * r.needed)
             throw std::runtime_error("range plan: inconsistent record");
-        if (slots == 0) slots = 1;
-        if (slots > r.needed) slots = (uint32_t)r.needed;
+        slots = clamp_slots(r.needed, slots);
         grow(arena, arena_cap, (size_t)r.scratch_bytes, false);
         bool fresh = state_slots < slots;
         if (fresh) {
@@ -356,23 +356,16 @@ struct RangeReader {
             state_slots = slots;
         }
         st.members_decoded = r.needed;
-        be.set_timing(true);
-        uint64_t nl = 0, nby[4];
-        double msby[4];
-        be.collect_timed(&nl);
-        for (uint64_t first = 0; first < r.needed; first += slots) {
-            const uint32_t count = r.needed - first < slots ? (uint32_t)(r.needed - first) : slots;
+        TimedBracket<BE> timed(be);
+        decode_rounds(r.needed, slots, [&](uint32_t first, uint32_t count) {
             if (!fresh) be.memset(state, 0, (size_t)count * DecodeLayout::kBytes);  // (alloc zeroed a new one)
             fresh = false;
-            be.timed_begin(2);
-            DecodeArgs a{d_src, ix.begin, ix.end, arena_off(), ix.out_len, arena, state, status(), (uint32_t)first, count};
+            DecodeArgs a{d_src, ix.begin, ix.end, arena_off(), ix.out_len, arena, state, status(), first, count};
             a.list = list();
             a.stop = stop();
             a.produced = produced();
-            be.launch_waves(count, DecodeMember{a}, DecodeMember::lds_bytes());
-            be.timed_end(2);
-            st.launches++;
-        }
+            launch_decode<DecodeMember>(be, a, st.launches);
+        });
         const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
         be.timed_begin(1);
         be.launch((size_t)RangeGather::units(sum, head),
@@ -381,17 +374,15 @@ struct RangeReader {
         std::vector<uint32_t> back((size_t)M * 3);
         be.d2h(back.data(), plan, (size_t)M * 12);
         st.host_waits++;
-        be.collect_timed(&nl, msby, nby);  // (the stream has drained: no further wait)
-        be.set_timing(false);
-        st.kernel_ms = msby[2];
-        st.gather_ms = msby[1];
+        const std::array<double, 4> ms = timed.finish();  // (the stream has drained: no further wait)
+        st.kernel_ms = ms[2];
+        st.gather_ms = ms[1];
         const uint32_t *h_stop = back.data(), *h_status = h_stop + M, *h_produced = h_status + M;
         for (uint64_t m = 0; m < M; m++) {
             if (!h_stop[m]) continue;
             if (h_status[m] != kDecOk) {
                 st.total_s = be.now() - t0;
-                throw std::runtime_error(h_status[m] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
-                                                                      : "invalid orz data (member " + std::to_string(m) + ", status " + std::to_string(h_status[m]) + ")");
+                throw decode_status_error(m, h_status[m]);
             }
             st.decoded_bytes += h_produced[m];
         }
@@ -483,8 +474,7 @@ struct RangeReader {
         }
         std::copy(h_stop.begin(), h_stop.end(), u_stop);
         const uint64_t need = todo.size();
-        if (slots == 0) slots = 1;
-        if (slots > need) slots = (uint32_t)need;
+        slots = clamp_slots(need, slots);
         bool fresh = false;
         if (last.uncached) {
             grow(arena, arena_cap, (size_t)arena_bytes, false);
@@ -504,26 +494,19 @@ struct RangeReader {
         const uint32_t *d_stop = (const uint32_t*)(d_cur + M), *d_list = d_stop + M;
         be.memset(status(), 0, (size_t)M * 8);  // status (kDecOk = 0), produced
         st.members_decoded = need;
-        be.set_timing(true);
-        uint64_t nl = 0, nby[4];
-        double msby[4];
-        be.collect_timed(&nl);
-        for (uint64_t first = 0; first < need; first += slots) {
-            const uint32_t count = need - first < slots ? (uint32_t)(need - first) : slots;
+        TimedBracket<BE> timed(be);
+        decode_rounds(need, slots, [&](uint32_t first, uint32_t count) {
             bool transient = false;
             for (uint32_t k = 0; k < count; k++) transient |= kind[todo[first + k]] == 2;
             if (transient && !fresh) be.memset(state, 0, (size_t)count * DecodeLayout::kBytes);  // (alloc zeroed a new one)
             if (transient) fresh = false;
-            be.timed_begin(2);
-            DecodeArgs a{d_src, ix.begin, ix.end, d_addr, ix.out_len, const_cast<uint8_t*>(d_src), state, status(), (uint32_t)first, count};
+            DecodeArgs a{d_src, ix.begin, ix.end, d_addr, ix.out_len, const_cast<uint8_t*>(d_src), state, status(), first, count};
             a.list = d_list;
             a.stop = d_stop;
             a.produced = produced();
             a.cursor = d_cur;
-            be.launch_waves(count, DecodeMemberCursor{a}, DecodeMemberCursor::lds_bytes());
-            be.timed_end(2);
-            st.launches++;
-        }
+            launch_decode<DecodeMemberCursor>(be, a, st.launches);
+        });
         const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
         be.timed_begin(1);
         be.launch((size_t)RangeGather::units(sum, head),
@@ -532,10 +515,9 @@ struct RangeReader {
         std::vector<uint32_t> back((size_t)M * 2);
         be.d2h(back.data(), status(), (size_t)M * 8);
         st.host_waits++;
-        be.collect_timed(&nl, msby, nby);  // (the stream has drained: no further wait)
-        be.set_timing(false);
-        st.kernel_ms = msby[2];
-        st.gather_ms = msby[1];
+        const std::array<double, 4> ms = timed.finish();  // (the stream has drained: no further wait)
+        st.kernel_ms = ms[2];
+        st.gather_ms = ms[1];
         const uint32_t *h_status = back.data(), *h_produced = h_status + M;
         int64_t failed = -1;
         for (uint32_t m : todo) {
@@ -548,9 +530,7 @@ struct RangeReader {
             if (kind[m] == 1) find_cursor(m)->produced = h_produced[m];
         }
         st.total_s = be.now() - t0;
-        if (failed >= 0)
-            throw std::runtime_error(h_status[failed] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
-                                                                       : "invalid orz data (member " + std::to_string(failed) + ", status " + std::to_string(h_status[failed]) + ")");
+        if (failed >= 0) throw decode_status_error((uint64_t)failed, h_status[failed]);
     }
 };
 

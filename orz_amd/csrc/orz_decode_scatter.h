@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "orz_decode_index.h"
+#include "orz_decode_drive.h"
 
 namespace orz {
 
@@ -99,19 +100,8 @@ void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_de
     const double t0 = be.now();
     const bool sizing = d_dsts == nullptr;
     if (!sizing && n_dsts && !d_caps) throw std::runtime_error("invalid argument: destinations without capacities");
-    struct Owned {  // the uploaded container, the plan and the decoder's state, freed on every way out
-        BE& be;
-        void* p[3] = {nullptr, nullptr, nullptr};
-        ~Owned() { for (void* q : p) if (q) be.free(q); }
-    } own{be};
-    const uint8_t* d_src = src;
-    if (!src_on_device) {
-        uint8_t* up = be.template alloc<uint8_t>(n, false);
-        own.p[0] = up;
-        be.h2d(up, src, n);
-        stats.host_waits++;
-        d_src = up;
-    }
+    DeviceBuffers<BE> own(be);  // the uploaded container, the plan and the decoder's state
+    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
     DeviceIndex<BE> ix(be);
     ix.build(d_src, n, table, offs, lens, n_table, true);
     stats.host_waits += ix.host_waits;
@@ -137,8 +127,7 @@ void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_de
     }
     // the plan's memory: dsts | caps (u64, ONE upload) | verdict | sizes (u32) | record, sizes and record read back together
     const size_t rec_at = ((size_t)M * 24 + 7) / 8 * 8;
-    uint8_t* plan = be.template alloc<uint8_t>(rec_at + sizeof(ScatterRecord), false);
-    own.p[1] = plan;
+    uint8_t* plan = own.template alloc<uint8_t>(rec_at + sizeof(ScatterRecord), false);
     uint64_t* p_dsts = (uint64_t*)plan;
     uint64_t* p_caps = p_dsts + M;
     uint32_t* p_verdict = (uint32_t*)(p_caps + M);
@@ -185,33 +174,12 @@ void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_de
     if (rec.status != kIxOk)
         throw DecodeCapacityError("the destination of member " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) +
                                   " bytes, too small for " + std::to_string(sizes[rec.bad]));
-    uint64_t nl = 0, nby[4];
-    double msby[4];
-    if (slots == 0) slots = 1;
-    if (slots > M) slots = (uint32_t)M;
-    uint8_t* d_state = be.template alloc<uint8_t>((size_t)slots * DecodeLayout::kBytes);
-    own.p[2] = d_state;
-    be.set_timing(true);
-    be.collect_timed(&nl);
-    for (uint64_t first = 0; first < M; first += slots) {
-        const uint32_t count = M - first < slots ? (uint32_t)(M - first) : slots;
-        if (first) be.memset(d_state, 0, (size_t)slots * DecodeLayout::kBytes);  // (alloc zeroes the first round)
-        be.timed_begin(2);
-        be.launch_waves(count, DecodeMember{DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, out, d_state, ix.status,
-                                                       (uint32_t)first, count}}, DecodeMember::lds_bytes());
-        be.timed_end(2);
-        stats.launches++;
-    }
-    be.collect_timed(&nl, msby, nby);
-    stats.kernel_ms = msby[2];
-    be.set_timing(false);
+    decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, out, nullptr, ix.status, 0, 0}, M, slots, own, stats);
     std::vector<uint32_t> status((size_t)M);
     be.d2h(status.data(), ix.status, (size_t)M * 4);
     stats.host_waits++;
     for (uint64_t m = 0; m < M; m++)
-        if (status[m] != kDecOk)
-            throw std::runtime_error(status[m] == kDecDeepTable ? "member with a 16-bit Huffman table: use the host decoder"
-                                                                : "invalid orz data (member " + std::to_string(m) + ", status " + std::to_string(status[m]) + ")");
+        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
     stats.total_s = be.now() - t0;
 }
 

@@ -15,7 +15,7 @@ STAT_NAMES = ("hits", "resumed", "fresh", "uncached", "evicted", "cursors", "byt
 def emu_lib():
     so = os.path.join(ROOT, "build", "libemu_reader_cache.so")
     src = os.path.join(ROOT, "tests", "emu", "emu_reader_cache.cpp")
-    srcs = [src] + [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_backend.cpp", "simt.h")]
+    srcs = [src] + [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_decode_range.cpp", "emu_backend.cpp", "simt.h")]
     srcs += [os.path.join(ROOT, "orz_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "orz_amd", "csrc"))]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         os.makedirs(os.path.dirname(so), exist_ok=True)

@@ -297,6 +297,10 @@ extern "C" int emu_encode(const uint8_t* src, size_t n, int depth, int lazy1, in
 }
 static std::string g_emu_err;
 extern "C" const char* emu_last_error() { return g_emu_err.c_str(); }  // message of the last emu_encode_fast that returned -1
+// the message of what a call caught, for the calls that hand it back in a buffer of the caller's (here and in the twins that include this file)
+static void put_err(const std::exception& e, char* err, size_t cap) {
+    if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
+}
 // the fast parse mode (orz_fast.h) on the emulation backend
 extern "C" int emu_encode_fast(const uint8_t* src, size_t n, int depth, int lazy1, int lazy2, unsigned tile, unsigned rounds,
                                uint8_t** dst, size_t* dst_len, unsigned long long* stats5) {
@@ -530,7 +534,7 @@ extern "C" int emu_decode_members(const uint8_t* src, size_t n, unsigned slots, 
         *dst = p; *dst_len = out.size(); *members = (size_t)st.members;
         return 0;
     } catch (const std::exception& e) {
-        if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
+        put_err(e, err, cap);
         return 1;
     }
 }
@@ -591,7 +595,7 @@ extern "C" int emu_decode_check(const uint8_t* stream, size_t n, const uint8_t* 
         chk.finish();
         return 0;
     } catch (const std::exception& e) {
-        if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
+        put_err(e, err, cap);
         return 1;
     }
 }

@@ -4,9 +4,6 @@
 #include "../../orz_amd/csrc/orz_decode_range.h"
 
 namespace {
-void put_err(const std::exception& e, char* err, size_t cap) {
-    if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
-}
 struct EmuReader {
     EmuBackend be;
     orz::RangeReader<EmuBackend>* rd = nullptr;

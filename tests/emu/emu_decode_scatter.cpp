@@ -3,12 +3,6 @@
 #include "emu_backend.cpp"
 #include "../../orz_amd/csrc/orz_decode_scatter.h"
 
-namespace {
-void put_err(const std::exception& e, char* err, size_t cap) {
-    if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
-}
-}  // namespace
-
 // the two plan launches alone, over arrays the caller made up: out_off / verdict (members entries) and rec3 = members, first bad
 // member, its verdict
 extern "C" void emu_scatter_plan(const uint64_t* dsts, const uint64_t* caps, const uint32_t* out_len, uint64_t members, uint64_t base,

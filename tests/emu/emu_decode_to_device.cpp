@@ -5,9 +5,6 @@
 #include "../../orz_amd/csrc/orz_decode_index.h"
 
 namespace {
-void put_err(const std::exception& e, char* err, size_t cap) {
-    if (err && cap) { std::strncpy(err, e.what(), cap - 1); err[cap - 1] = 0; }
-}
 void copy_index(uint64_t m, const uint64_t* b, const uint64_t* e, const uint64_t* o, const uint32_t* l, size_t cap, uint64_t* begin,
                 uint64_t* end, uint64_t* off, uint32_t* len) {
     for (uint64_t k = 0; k < m && k < cap; k++) { begin[k] = b[k]; end[k] = e[k]; off[k] = o[k]; len[k] = l[k]; }
