@@ -281,6 +281,60 @@ int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on
                                size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
 uint64_t orz_decode_members_scatter_host_waits(void);
 
+/* ---- tensors as byte planes, a member per plane (orz_planes.h) -----------------------------------------
+ * For typed data: plane p of a segment of seg_elem-byte elements is byte p of every element (the bytes at offsets p, p + e,
+ * p + 2 e, ...).  The predictable bytes of multi-byte elements -- sign and exponent, the high bytes of ids and counts -- then
+ * stand next to each other instead of between noise bytes: weights shrink by about a tenth, ids and counts severalfold (DESIGN
+ * 9).  The format does not change: every plane is an ordinary member, and a segment contributes seg_elem consecutive members,
+ * plane 0 first (an element size of 1: its bytes unchanged as one member; an empty segment: seg_elem empty members).
+ * seg_elem[k] is 1, 2, 4 or 8 and divides seg_len[k].  The stream of a plane is byte for byte what
+ * orz_members_encode_segments_to_device writes for those plane bytes as a segment of their own.
+ * orz_members_bound_planes: the sum of seg_elem[k] * orz_stream_bound(seg_len[k] / seg_elem[k]), a d_cap that always suffices.
+ *   A stream's bound is dominated by about 1 MiB a member for small inputs, so callers with many small tensors should size
+ *   d_dst themselves instead.
+ * orz_members_encode_planes_to_device: offs / lens (host arrays of sum(seg_elem) entries, segment by segment, plane 0 first) say
+ *   where each member's stream lies in d_dst.  Workers, arenas and waits are those of orz_members_encode_segments_to_device; it
+ *   costs more: ONE device buffer for the call's duration that holds the planes of every segment with seg_elem > 1 (plane
+ *   pitches rounded up to 16, each segment's planes at a multiple of 256) and, with src_on_device == 0, a copy of every segment
+ *   (host input is uploaded first, every segment of it, and then takes the path of device-resident input); one upload of the
+ *   descriptor table and ONE PlaneSplit launch for all segments, waited for once.  Device-resident segments with seg_elem == 1
+ *   are encoded where they lie.
+ * n_segs == 0: ORZ_OK, nothing launched.  ORZ_EINVAL, before anything reaches the device: what
+ * orz_members_encode_segments_to_device refuses, a NULL seg_elem with n_segs > 0, an element size other than 1, 2, 4, 8, a
+ * length its element size does not divide.  ORZ_ENOMEM when d_dst fills up or the staging buffer cannot be allocated. */
+size_t orz_members_bound_planes(const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs);
+int orz_members_encode_planes_to_device(orz_members*, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
+                                        size_t n_segs, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens);
+/* PLANES MERGED ON DECODE.  src / n / src_on_device / offs / lens / n_members exactly as for orz_decode_members_scatter.
+ * Destination j (d_caps[j] bytes at d_dsts[j] on `device`; host arrays of n_dsts entries) takes the next elems[j] members as the
+ * byte planes of elements of elems[j] bytes; out_lens (optional, n_dsts entries) = each destination's size in bytes, plane size
+ * x elems[j], filled also when the call fails with ORZ_ENOMEM; *n_members_out = members.  d_dsts == NULL only sizes (elems is
+ * still needed): nothing is decoded.  A destination of 0 bytes may have any pointer and capacity 0.
+ *   ORZ_EINVAL, all found before any decode launch: what orz_decode_members_scatter refuses of a container; the sum of elems
+ *     different from the member count ("X planes for Y members"); an element size other than 1, 2, 4, 8; the planes of one
+ *     destination not all of the same decoded size (the destination and the first member that differs are named); a NULL
+ *     destination that has bytes; two destinations that have bytes overlap (whole capacities count); a destination overlaps a
+ *     device-resident src.
+ *   ORZ_ENOMEM naming the first destination whose capacity is below its size: NOTHING has been written to any destination.  Also
+ *     when the staging buffer cannot be allocated.
+ *   ORZ_EINVAL naming the member, after the launches: payload damage (the content of the destinations is then unspecified).
+ * Nothing outside [d_dsts[j], d_dsts[j] + out_lens[j]) is written for any j, and the output does not depend on what the buffers
+ * held.  Members of destinations with elems == 1 decode straight into them; the others decode into a staging buffer (freed
+ * before the call returns: at most the container's decoded size plus 32 bytes a member; none when every elems[j] is 1) and ONE
+ * PlaneMerge launch queued behind the decode launches (ORZ_DECODE_SLOTS members in flight) writes their destinations.  Host
+ * waits: those of orz_decode_members_scatter for the same container, whatever the number of destinations -- 4, and one more each
+ * for a member table and a host-resident src.  orz_decode_members_planes_host_waits: that count for the calling thread's last
+ * orz_decode_members_planes call. */
+int orz_decode_members_planes(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                              size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, size_t n_dsts,
+                              size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_members_planes_host_waits(void);
+/* A measuring hook (tools/dev/planes_bench.py), not a data path: `reps` launches of PlaneSplit (merge == 0) or PlaneMerge over ONE
+ * tensor of `count` elements of `elem` bytes (2, 4 or 8) -- interleaved at d_inter, planes at d_planes with a pitch of count
+ * rounded up to 16, both on `device` and owned by the caller -- between two events after one warming launch; *ms = milliseconds
+ * a launch. */
+int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms);
+
 /* ---- byte ranges of a members container (orz_decode_range.h) ------------------------------------------
  * A reader indexes a container ONCE (on the device, as orz_decode_members_to_device does) and then serves reads of byte
  * ranges of its DECODED data.  A read decodes only the members its non-empty ranges touch, each once per call however many

@@ -379,6 +379,66 @@ class MemberEncoder:
                                                  out.data_ptr(), out.numel(), src_on_device=on_dev)
         return (out[: max(o + ln for o, ln in members)] if trim else out), members
 
+    def bound_planes(self, lengths, elems):
+        """device bytes that always hold the plane members of segments of these lengths and element sizes
+        (orz_members_bound_planes).  About 1 MiB a member for small segments: with many small tensors pass an `out` of your own."""
+        n = len(lengths)
+        if len(elems) != n:
+            raise ValueError("one element size per length")
+        arr = (ctypes.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+        el = (ctypes.c_uint32 * max(n, 1))(*[int(e) for e in elems])
+        return int(self._lib.orz_members_bound_planes(arr, el, n))
+
+    def encode_planes_to_device(self, seg_ptrs, seg_lens, seg_elems, dst_ptr, dst_cap, src_on_device=True):
+        """orz_members_encode_planes_to_device on raw addresses: segment k is the seg_lens[k] bytes at seg_ptrs[k], elements of
+        seg_elems[k] bytes (1, 2, 4 or 8); it becomes seg_elems[k] members, one per byte plane, plane 0 first.  Returns
+        [(offset, length)] per member, segment by segment, into the buffer at `dst_ptr`."""
+        if len(seg_elems) != len(seg_ptrs) or len(seg_lens) != len(seg_ptrs):
+            raise ValueError("one length and one element size per segment")
+        ptrs, lengths, n = self._segment_arrays([int(p) for p in seg_ptrs], [int(x) for x in seg_lens])
+        el = (ctypes.c_uint32 * max(n, 1))(*[int(e) for e in seg_elems])
+        nm = sum(int(e) for e in seg_elems if 0 < int(e) <= 8)
+        offs, lens = (ctypes.c_size_t * max(nm, 1))(), (ctypes.c_size_t * max(nm, 1))()
+        rc = self._lib.orz_members_encode_planes_to_device(self._h, ptrs, lengths, el, n, 1 if src_on_device else 0,
+                                                           ctypes.c_void_p(int(dst_ptr)), int(dst_cap), offs, lens)
+        _check(rc, "orz_members_encode_planes_to_device")
+        return [(offs[k], lens[k]) for k in range(nm)]
+
+    def encode_tensor_planes(self, tensors, out=None):
+        """Each tensor of `tensors` as the byte planes of its elements, a member per plane (plane p = byte p of every element):
+        tensor k contributes element_size() consecutive members, plane 0 first.  For typed data -- weights shrink by about a
+        tenth against encode_tensors, ids and counts severalfold -- and a tensor's planes decode side by side.  Tensors, devices
+        and `out` as for encode_tensors; an element size above 8 raises ValueError.  Returns (container, members, elems):
+        `members` [(offset, length)] per plane, `elems` [element size of each tensor]: what decode_planes_into takes."""
+        import torch
+
+        if len(self._devices) != 1:
+            raise ValueError("device-resident output needs an encoder on one GPU")
+        dev = torch.device("cuda", self._devices[0])
+        tensors = list(tensors)
+        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
+            raise ValueError("tensors must be contiguous torch tensors")
+        on_dev = bool(tensors) and tensors[0].is_cuda
+        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
+            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
+        elems = [t.element_size() for t in tensors]
+        if any(e > 8 for e in elems):
+            raise ValueError("elements of more than 8 bytes have no byte planes here: view the tensor as a narrower dtype")
+        lengths = [t.numel() * t.element_size() for t in tensors]
+        if out is None:
+            out = torch.empty(self.bound_planes(lengths, elems), dtype=torch.uint8, device=dev)
+            trim = True
+        else:
+            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
+            trim = False
+        if not tensors:
+            return (out[:0] if trim else out), [], []
+        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        members = self.encode_planes_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
+                                               out.data_ptr(), out.numel(), src_on_device=on_dev)
+        return (out[: max(o + ln for o, ln in members)] if trim else out), members, elems
+
     def close(self):
         if self._h:
             self._lib.orz_members_free(self._h)
@@ -530,6 +590,61 @@ def decode_members_into(src, outs, device=0, members=None, stats=False):
     if stats:
         d = st.as_dict()
         d["host_waits"] = int(lib.orz_decode_members_scatter_host_waits())
+        return res, d
+    return res
+
+
+def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False):
+    """decode plane members ON THE GPU and merge them (orz_decode_members_planes): `outs[k]` takes the next elems[k] members as
+    the byte planes of its elements -- what MemberEncoder.encode_tensor_planes wrote.  `src` and `members` as for
+    decode_members_into; `outs`: contiguous tensors on cuda:`device`, each at least as large as its planes together; `elems`:
+    the element size of each (1, 2, 4 or 8), by default that of the tensors.  Raises OrzError, with nothing written to any tensor,
+    when a size does not fit, the planes are not as many as the members, a tensor's planes differ in size or two tensors overlap.
+    Returns [decoded size of each tensor] (and the stats dict, with `host_waits`)."""
+    import torch
+
+    lib = _native.load()
+    dev = torch.device("cuda", int(device))
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError("src must be a contiguous uint8 tensor")
+        if src.is_cuda and src.device != dev:
+            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
+        keep, on_dev = src, src.is_cuda
+        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
+    else:
+        data = bytes(src)
+        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    outs = list(outs)
+    if any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in outs):
+        raise ValueError("outs must be contiguous tensors on %s" % dev)
+    elems = [t.element_size() for t in outs] if elems is None else [int(e) for e in elems]
+    if len(elems) != len(outs):
+        raise ValueError("one element size per tensor")
+    if members is None:
+        offs = lens = None
+        nt = 0
+    else:
+        nt = len(members)
+        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
+        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
+    nd = len(outs)
+    caps = (ctypes.c_size_t * max(nd, 1))(*[t.numel() * t.element_size() for t in outs])
+    dsts = (ctypes.c_void_p * max(nd, 1))(*[(t.data_ptr() if t.numel() else None) for t in outs])
+    el = (ctypes.c_uint32 * max(nd, 1))(*[e & 0xFFFFFFFF for e in elems])
+    sizes = (ctypes.c_size_t * max(nd, 1))()
+    nm = ctypes.c_size_t()
+    st = _native.DecodeStats()
+    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+    rc = lib.orz_decode_members_planes(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, nd, sizes, ctypes.byref(nm),
+                                       ctypes.byref(st))
+    _check(rc, "orz_decode_members_planes")
+    del keep
+    res = [sizes[k] for k in range(nd)]
+    if stats:
+        d = st.as_dict()
+        d["host_waits"] = int(lib.orz_decode_members_planes_host_waits())
         return res, d
     return res
 

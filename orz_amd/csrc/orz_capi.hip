@@ -20,6 +20,7 @@
 #include "orz_decode_range.h"
 #include "orz_decode_scatter.h"
 #include "orz_host_decode.h"
+#include "orz_planes.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
 
@@ -726,6 +727,97 @@ int orz_members_encode_segments_to_device(orz_members* m, const void* const* seg
         return fail(ORZ_ENOMEM, e.what());
     }
 }
+// ---- tensors as byte planes (orz_planes.h): the planes of every segment staged in ONE device buffer by ONE PlaneSplit launch,
+// then the segment call's path over the planes as device-resident items
+size_t orz_members_bound_planes(const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs) {
+    size_t total = 0;
+    for (size_t k = 0; seg_len && seg_elem && k < n_segs; k++)
+        if (seg_elem[k]) total += (size_t)seg_elem[k] * orz::stream_bound(seg_len[k] / seg_elem[k]);
+    return total;
+}
+int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
+                                        size_t n_segs, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens) {
+    struct Staging {  // the call's one device buffer: the descriptor table, then the planes (and the uploads of host segments)
+        void* p = nullptr;
+        ~Staging() { if (p) (void)hipFree(p); }
+    } staging;
+    try {
+        std::vector<MemberItem> segs;
+        if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, segs)) return fail(ORZ_EINVAL, why);
+        if (n_segs && !seg_elem) return fail(ORZ_EINVAL, "null element sizes");
+        for (size_t k = 0; k < n_segs; k++) {
+            if (!orz::plane_elem_ok(seg_elem[k]))
+                return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " has elements of " + std::to_string(seg_elem[k]) + " bytes (1, 2, 4 or 8)");
+            if (segs[k].len % seg_elem[k])
+                return fail(ORZ_EINVAL, "the " + std::to_string(segs[k].len) + " bytes of segment " + std::to_string(k) + " are no multiple of its element size " +
+                                            std::to_string(seg_elem[k]));
+        }
+        if (!n_segs) return ORZ_OK;
+        if (!d_dst || !offs || !lens) return fail(ORZ_EINVAL, "bad argument");
+        if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
+        if (src_on_device)
+            for (size_t k = 0; k < n_segs; k++)
+                if (segs[k].len && d_cap && segs[k].p < d_dst + d_cap && d_dst < segs[k].p + segs[k].len)
+                    return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
+        // the staging buffer's layout: table | per segment, at multiples of 256: [its upload] [its planes]
+        size_t n_rows = 0, n_items = 0;
+        for (size_t k = 0; k < n_segs; k++) { n_rows += seg_elem[k] > 1; n_items += seg_elem[k]; }
+        const auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+        size_t at = up256(orz::plane_table_bytes(n_rows));
+        std::vector<size_t> raw_at(n_segs, 0), planes_at(n_segs, 0);
+        for (size_t k = 0; k < n_segs; k++) {
+            if (!src_on_device && segs[k].len) { raw_at[k] = at; at = up256(at + segs[k].len); }
+            if (seg_elem[k] > 1 && segs[k].len) { planes_at[k] = at; at = up256(at + (size_t)seg_elem[k] * orz::plane_pitch(segs[k].len / seg_elem[k])); }
+        }
+        const bool need = n_rows || !src_on_device;
+        orz::HipBackend& be = *m->workers[0]->be;
+        uint8_t* stage = nullptr;
+        if (need) {
+            ORZ_HIP_CHECK(hipSetDevice(be.device()));
+            if (hipMalloc(&staging.p, at) != hipSuccess) {
+                (void)hipGetLastError();
+                staging.p = nullptr;
+                return fail(ORZ_ENOMEM, "no device memory for " + std::to_string(at) + " bytes of plane staging");
+            }
+            stage = (uint8_t*)staging.p;
+        }
+        std::vector<MemberItem> items;
+        items.reserve(n_items);
+        std::vector<orz::PlaneRow> rows;
+        rows.reserve(n_rows);
+        for (size_t k = 0; k < n_segs; k++) {
+            const uint32_t e = seg_elem[k];
+            const size_t count = segs[k].len / e;
+            const uint8_t* d_seg = segs[k].p;
+            if (!src_on_device && segs[k].len) {
+                be.h2d(stage + raw_at[k], segs[k].p, segs[k].len);
+                d_seg = stage + raw_at[k];
+            }
+            if (e == 1) {
+                items.push_back(MemberItem{count ? d_seg : nullptr, count});
+                continue;
+            }
+            const size_t pitch = orz::plane_pitch(count);
+            for (uint32_t p = 0; p < e; p++) items.push_back(MemberItem{count ? stage + planes_at[k] + p * pitch : nullptr, count});
+            rows.push_back(orz::PlaneRow{(uint64_t)(uintptr_t)d_seg, (uint64_t)(uintptr_t)(stage + planes_at[k]), count, e});
+        }
+        if (!rows.empty()) {
+            std::vector<uint64_t> image;
+            uint64_t units = 0;
+            const orz::PlaneTable t = orz::plane_table_image(rows, stage, image, units);
+            if (units) {
+                be.h2d(stage, image.data(), image.size() * 8);
+                be.launch((size_t)units, orz::PlaneSplit{t, units});
+                be.sync();  // (the workers read the planes on streams of their own)
+            }
+        }
+        return members_encode_device(m, items, 1, d_dst, d_cap, offs, lens);
+    } catch (const std::bad_alloc& e) {
+        return fail(ORZ_ENOMEM, e.what());
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENODEV, e.what());
+    }
+}
 int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len, size_t* n_members_out) {
     if ((!src && n) || !dst || !dst_len) return fail(ORZ_EINVAL, "bad argument");
     try {
@@ -827,6 +919,60 @@ int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on
     return rc;
 }
 uint64_t orz_decode_members_scatter_host_waits(void) { return g_scatter_waits; }
+
+thread_local uint64_t g_planes_waits = 0;
+int orz_decode_members_planes(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                              size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, size_t n_dsts,
+                              size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats) {
+    g_planes_waits = 0;
+    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && !elems)) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    uint64_t members = 0;
+    orz::DecodeScatterStats st;
+    const int rc = mapped([&] {
+        orz::HipBackend be(device);
+        orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
+                                   n_members, d_dsts, (const uint64_t*)d_caps, elems, n_dsts, (uint64_t*)out_lens, members, st, decode_slots());
+    });
+    g_planes_waits = st.host_waits;
+    if (n_members_out) *n_members_out = (size_t)members;
+    if (rc == ORZ_OK) put_stats(stats, st);
+    return rc;
+}
+uint64_t orz_decode_members_planes_host_waits(void) { return g_planes_waits; }
+int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {
+    if (!d_inter || !d_planes || !count || !ms || reps < 1 || (elem != 2 && elem != 4 && elem != 8)) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    try {
+        orz::HipBackend be(device);
+        orz::DeviceBuffers<orz::HipBackend> own(be);
+        std::vector<orz::PlaneRow> rows{orz::PlaneRow{(uint64_t)(uintptr_t)d_inter, (uint64_t)(uintptr_t)d_planes, count, elem}};
+        uint8_t* d_table = own.alloc<uint8_t>(orz::plane_table_bytes(1), false);
+        std::vector<uint64_t> image;
+        uint64_t units = 0;
+        const orz::PlaneTable t = orz::plane_table_image(rows, d_table, image, units);
+        be.h2d(d_table, image.data(), image.size() * 8);
+        ORZ_HIP_CHECK(hipEventCreate(&ev.a));
+        ORZ_HIP_CHECK(hipEventCreate(&ev.b));
+        for (int r = -1; r < reps; r++) {  // (the first launch warms up)
+            if (r == 0) ORZ_HIP_CHECK(hipEventRecord(ev.a, be.stream()));
+            if (merge) be.launch((size_t)units, orz::PlaneMerge{t, units});
+            else be.launch((size_t)units, orz::PlaneSplit{t, units});
+        }
+        ORZ_HIP_CHECK(hipEventRecord(ev.b, be.stream()));
+        ORZ_HIP_CHECK(hipEventSynchronize(ev.b));
+        float total = 0;
+        ORZ_HIP_CHECK(hipEventElapsedTime(&total, ev.a, ev.b));
+        *ms = (double)total / reps;
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENODEV, e.what());
+    }
+}
 
 // ------------------------------------------------------------------------------ byte ranges of a container
 struct orz_reader {

@@ -1,10 +1,11 @@
 // orz_decode_drive.h -- what the host drivers of the device decoder share (host side only, templated on the backend).
 //
-// Five drivers launch DecodeMember / DecodeMemberCursor: decode_members_device (orz_decode_device.h), decode_members_to_device
-// (orz_decode_index.h), decode_members_scatter (orz_decode_scatter.h), RangeReader::read and ::read_cached (orz_decode_range.h).
+// Six drivers launch DecodeMember / DecodeMemberCursor: decode_members_device (orz_decode_device.h), decode_members_to_device
+// (orz_decode_index.h), decode_members_scatter (orz_decode_scatter.h), decode_members_planes (orz_planes.h), RangeReader::read and
+// ::read_cached (orz_decode_range.h).
 // Here is what is literally the same in all of them: the message of a failed member, the owner of a call's device buffers, the
 // upload of a host container, the timing bracket, the loop over rounds of `slots` members and the launch of one round -- and
-// decode_all, the whole sequence of the three one-shot drivers.  What differs stays with its driver: where the bytes go, how the
+// decode_all, the whole sequence of the four one-shot drivers.  What differs stays with its driver: where the bytes go, how the
 // statuses come back, and the readers' rules for zeroing a state that outlives the call.
 //
 // orz_decode_device.h includes this header below the decoder's types; include that one.
