@@ -22,8 +22,18 @@
 // and the reference's slide (src/lib.rs:119-124; Bucket::forward, src/matcher.rs:82-87) is a counter -- a node whose
 // position has left the window (window offset <= 0 after the slides so far) is dead, as `pos = 0` is in the reference.
 // Members of any number of blocks below 4 GiB decode here (round 4; before, one block: the default 64 MiB members of
-// `orz_members_encode` were refused).  One difference to the reference on MALFORMED streams only: a match that names a
-// dead node is rejected as invalid data here (the reference copies from window offset 0).
+// `orz_members_encode` were refused).
+//
+// Differences to the reference, all on streams no encoder writes (DESIGN.md 9 has the list with its reasons; tests/
+// test_freeparse_decoders.py holds every other legal stream to the reference's bytes):
+//   - a match that names a dead node is rejected as invalid data (the reference copies from window offset 0);
+//   - a 16-bit Huffman table is kDecDeepTable: the host decoder takes such a member;
+//   - a census that lists a symbol twice is invalid data;
+//   - a partial decode without a cursor (DecodeArgs::stop) refuses, as invalid data, a chunk whose end field lies below the stop
+//     and in which, after an item that overran the field, another item starts at or beyond the stop;
+//   - items of 256..367 bytes pass the length check although the reference's len_expected is 8 bits wide: no test holds them to anything.
+// None of them is kDecOk with other bytes.  An item that runs past the member's announced end IS followed exactly: its bytes
+// beyond the end go to DecodeLayout::kOver, where the copy of an overlapping match finds them again.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -56,7 +66,11 @@ struct DecodeLayout {  // byte offsets into one member's state blob
     static constexpr size_t kLut = kWords + 65536;            // 3 tables x 32768 x u16: (symbol << 4) | length
     static constexpr size_t kLens = kLut + (size_t)3 * 32768 * 2;  // scratch: code lengths being read
     static constexpr size_t kOrder = kLens + 512;              // scratch: census order (389 x u16)
-    static constexpr size_t kBytes = (kOrder + 1024 + 255) / 256 * 256;
+    // the bytes of the one item that crosses `lim` (run()) at or beyond it: they have no place in the output, and an overlapping
+    // match reads them back while it copies -- the reference has them in its window (an item runs at most kMaxLen + 126 bytes past lim)
+    static constexpr size_t kOver = kOrder + 1024;
+    static constexpr uint32_t kOverBytes = 512;
+    static constexpr size_t kBytes = (kOver + kOverBytes + 255) / 256 * 256;
 };
 
 struct DecodeLds {  // byte offsets into a member's LDS (DecodeMember::lds_bytes())
@@ -274,6 +288,7 @@ struct DecodeMemberBody {
         uint16_t* lut = (uint16_t*)(st + DecodeLayout::kLut);
         uint8_t* lens = st + DecodeLayout::kLens;
         uint16_t* order = (uint16_t*)(st + DecodeLayout::kOrder);
+        uint8_t* over = st + DecodeLayout::kOver;
         const bool resumed = rec && rec->live;
         if (!resumed)
             for (uint32_t c = 0; c < 512; c++) rank_sum[c] = 1000000;  // SymRankCoder::new, src/symrank.rs:22-29
@@ -282,9 +297,11 @@ struct DecodeMemberBody {
         const uint32_t out_len = a.out_len[m];
         // With a stop the member ends, kDecOk, at the first chunk or item that STARTS at or beyond lim, and no byte at or beyond
         // lim is stored or loaded: `out` need hold lim bytes only.  Decoding is causal, so the bytes below lim are those of the whole
-        // decode; what the stream holds behind that point is never looked at.  An item may start beyond lim and the member go on
-        // only inside a chunk whose end field lies below lim (its items overran the field, the cut below takes them back: crafted
-        // streams, no encoder's) -- bytes that are not stored read as zero there, as bytes beyond out_len always did.
+        // decode; what the stream holds behind that point is never looked at.  ONE item may cross lim and the member go on: the last
+        // item before out_len, or an item of a chunk whose end field lies below lim (it overran the field, the cut below takes it
+        // back: crafted streams, no encoder's).  What that item has at or beyond lim goes to the blob's kOver area, where the copy of
+        // an overlapping match finds it again, as the reference finds it in its window.  A second item that STARTS at or beyond lim
+        // in such a chunk is refused (kDecBadData): its bytes would have no place, and none are made up.
         //
         // A CURSOR (rec != nullptr) separates the two things lim is: the decode SUSPENDS at the first chunk or item that starts at or
         // beyond the stop (slim), and stores every item whole up to out_len (lim).  A decode that is thrown away may leave the bytes
@@ -372,7 +389,12 @@ struct DecodeMemberBody {
             in_chunk = false;
             const bool may_stop = part && (uint64_t)end_field + slid >= (uint64_t)slim + kPre;  // (no cut of this chunk goes back below the stop)
             for (; it < n_items; it++) {
-                if (may_stop && spos - kPre + slid >= slim) return reached(spos - kPre + slid, true, at);
+                if (part && spos - kPre + slid >= slim) {
+                    if (may_stop) return reached(spos - kPre + slid, true, at);
+                    // the chunk's end field lies below the stop and a SECOND item starts beyond it (crafted streams): a decode that
+                    // stores nothing beyond the stop cannot follow the chunk -- refused, never guessed.  A cursor stores everything.
+                    if (!rec) return kDecBadData;
+                }
                 const uint32_t r = sym(br, lut + (after_literal ? 32768 : 0), prim + (after_literal ? 4096 : 0), ml[after_literal ? 1 : 0]);
                 if (r >= kSyms) return kDecBadData;
                 // hash1(spos-1), hash2(spos-1) from the last three bytes (src/lz.rs:482-492)
@@ -481,11 +503,21 @@ struct DecodeMemberBody {
                         }
                         if (len >= 8) tail = __builtin_bswap64(endw);
                         else tail = (tail << (8 * len)) | (__builtin_bswap64(first) >> (64 - 8 * len));
-                    } else {
+                    } else if (opos + len <= lim) {
                         for (uint32_t k = 0; k < len; k++) {  // overlap-safe forward copy
                             const uint32_t sp = src + k;
                             const uint8_t b = sp < lim ? out[sp] : 0;
                             if (opos + k < lim) out[opos + k] = b;
+                            tail = (tail << 8) | b;
+                        }
+                    } else {
+                        // the same copy for the one item that crosses lim.  It starts below lim (checked above) and is at most
+                        // kMaxLen + 127 bytes long: what it has at or beyond lim fits `over`, where its own later bytes find it again
+                        for (uint32_t k = 0; k < len; k++) {
+                            const uint32_t sp = src + k;
+                            const uint8_t b = sp < lim ? out[sp] : over[sp - lim];
+                            if (opos + k < lim) out[opos + k] = b;
+                            else over[opos + k - lim] = b;
                             tail = (tail << 8) | b;
                         }
                     }
