@@ -168,6 +168,26 @@ int orz_stream_set_item_trace(orz_stream*, int on);
 /* copies up to cap items to out, returns the total number traced (or a negative error) */
 long orz_stream_get_item_trace(orz_stream*, orz_item* out, size_t cap);
 
+/* FOR TESTS of the validity gate: overwrite named fields of named items of the NEXT encode on this stream, after the parse and
+ * before the items are coded -- the way a defect of the parse or of the item stage would appear, or (SRC) another legal parse.
+ * `block` is the counter orz_item.block reports, `pos` the window offset of an item start of that block.  TYPE (low two bits of
+ * the item type: 0 WORD, 1 literal), LEN (match length) and SRC (window offset of the match source) go into the parse's
+ * per-position arrays before the len_min bookkeeping; LMV (the len_min a match is coded against) behind that bookkeeping; SYM,
+ * CTX, AL (bit 0 of after_literal), ENC, ROB (robits | robitlen << 12), UNL into the item arrays before they are ranked, ORD into
+ * the parse's ring ordinal at pos.  The list holds for one encode, whether it succeeds or not; n == 0 clears it.  A non-empty
+ * list is announced on stderr like the environment's fault-injection hooks.  A patch that finds no item start at (block, pos)
+ * is not applied and the encode fails for that reason: "item patches: ... were not applied".  ORZ_EINVAL, before anything
+ * reaches the device, for every value a later kernel would index with out of range: an unknown field, pos outside the block's
+ * new bytes, TYPE > 1 (no patch makes a match of an item without a source), LEN > 240, SRC outside [1, pos), SYM >= 389,
+ * CTX >= 512, AL > 1, ENC >= 240, UNL > 255, LMV > 127, ROB with more than 12 extra bits or bits above their count; more than
+ * 65536 patches.  Set the list after any call that reconfigures the stream (orz_stream_set_mode, orz_stream_set_tuning). */
+enum { ORZ_PATCH_TYPE = 0, ORZ_PATCH_LEN, ORZ_PATCH_SRC, ORZ_PATCH_SYM, ORZ_PATCH_CTX, ORZ_PATCH_AL, ORZ_PATCH_ENC, ORZ_PATCH_ROB,
+       ORZ_PATCH_UNL, ORZ_PATCH_ORD, ORZ_PATCH_LMV };
+typedef struct {
+    uint32_t block, pos, field, value;
+} orz_item_patch;
+int orz_stream_set_item_patches(orz_stream*, const orz_item_patch* patches, size_t n);
+
 /* FOR TESTS: the static tables of one block of the fast parse (orz_fast.h, FastArgs), read between the block's prep kernels and
  * its first round.  name == NULL arms the capture for the `arm_block`-th encode_block call (0 = the first; a block encoded in
  * units makes one call per unit) of the NEXT encode on this stream, arm_block < 0 disarms; returns 0.  An armed encode waits

@@ -174,6 +174,17 @@ class StreamEncoder:
                        ("src", "<u4")])
         return np.frombuffer(buf, dtype=dt, count=n).copy()
 
+    PATCH_FIELDS = {"TYPE": 0, "LEN": 1, "SRC": 2, "SYM": 3, "CTX": 4, "AL": 5, "ENC": 6, "ROB": 7, "UNL": 8, "ORD": 9, "LMV": 10}
+
+    def set_item_patches(self, patches):
+        """FOR TESTS of the validity gate (orz_stream_set_item_patches): [(block, pos, field, value)], field a name of PATCH_FIELDS
+        or its number, overwrite those fields of those items in the next encode() only.  An empty list clears."""
+        import numpy as np
+
+        arr = np.array([(b, p, self.PATCH_FIELDS.get(f, f), v) for b, p, f, v in patches], dtype="<u4").reshape(-1, 4)
+        _check(self._lib.orz_stream_set_item_patches(self._h, arr.ctypes.data if len(arr) else None, len(arr)),
+               "orz_stream_set_item_patches")
+
     # the tables orz_stream_fast_tables hands out, and what they hold
     FAST_TABLES = {"hpos": "<u4", "wsnap": "u1", "epos": "<u4", "keys": "<u4", "idx": "<u4", "runstart": "<u4", "rlen": "u1", "vbits": "<u8",
                    "stext": "<u8", "cl": "<u8", "ccnt": "<u4", "rows": "u1", "rdist": "<u8", "kpos": "<u4", "kkeys": "<u4", "krun": "<u4",

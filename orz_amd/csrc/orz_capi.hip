@@ -333,6 +333,10 @@ static orz::StreamEncoder<orz::HipBackend>::DeviceResult stream_encode_device(or
         orz::FastTableCapture& c;
         ~Disarm() { c.arm = -1; }
     } disarm{s->tables};
+    struct ClearPatches {  // (tests) an item patch list holds for ONE encode, however it ends
+        orz_stream* s;
+        ~ClearPatches() { if (s->enc) s->enc->clear_item_patches(); }
+    } clear_patches{s};
     const auto r = orz::encode_stream_device(*s->enc, be, (const uint8_t*)src, n, src_on_device != 0, d_dst, d_cap, pinned);
     if (stats) {
         float total = 0;
@@ -414,6 +418,23 @@ long orz_stream_get_item_trace(orz_stream* s, orz_item* out, size_t cap) {
         out[i] = it;
     }
     return (long)n;
+}
+
+// (tests of the validity gate) item patches of the next encode, see include/orz_hip.h and orz_verify.h
+int orz_stream_set_item_patches(orz_stream* s, const orz_item_patch* patches, size_t n) {
+    if (!s || !s->enc) return fail(ORZ_EINVAL, "null stream");
+    static_assert(sizeof(orz_item_patch) == sizeof(orz::ItemPatch), "orz_item_patch is the device's ItemPatch");
+    try {
+        ORZ_HIP_CHECK(hipSetDevice(s->be->device()));
+        s->enc->set_item_patches(reinterpret_cast<const orz::ItemPatch*>(patches), n);
+        return ORZ_OK;
+    } catch (const std::invalid_argument& e) {
+        return fail(ORZ_EINVAL, e.what());
+    } catch (const std::bad_alloc&) {
+        return fail(ORZ_ENOMEM, "out of memory");
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENODEV, e.what());
+    }
 }
 
 // (tests) the static tables of one block of the fast parse, see include/orz_hip.h

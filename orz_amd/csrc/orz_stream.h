@@ -1335,14 +1335,17 @@ class StreamEncoder {
         if (nitems > t.cap) grow_tail_set(t, nitems);  // (the set is idle: its last block was collected above)
         be_.launch(n, CompactPos32{f32_, sc32_, n, kPre, t.ipos});
         if (inject_kind_ && inject_kind_ != kViLenMin2) be_.launch(1, VerInjectK{inject_kind_, inject_nth_, t.ipos, nitems, TY_, ML_, SRC_, ORD_, win, S_});  // (tests of the gate)
+        apply_item_patches(kIpAtParse, t, nitems);  // (tests of the gate: nothing is launched unless a list is set)
         // len_min of each reference (keys reuse the sort buffers)
         be_.launch(nitems, LenMinKeys{t.ipos, TY_, SRC_, nitems, entA_});
         const uint64_t* lk = be_.sort_u64(entA_, entB_, nitems, 2 * kPosBits, kPosBits);  // (the keys come in position order: a stable sort by source)
         be_.launch(nitems, LenMinEval{lk, nitems, ML_, LENMIN_, LMV_});
         be_.launch(nitems, LenMinCommit{lk, nitems, ML_, LMV_, LENMIN_});
         if (inject_kind_ == kViLenMin2) be_.launch(1, VerInjectLmv{inject_nth_, t.ipos, nitems, TY_, LMV_});  // (tests of the gate)
+        apply_item_patches(kIpAtLenMin, t, nitems);
         be_.launch(nitems, ItemSyms{win, t.ipos, nitems, TY_, ML_, W0_, LMV_, SRC_, ORD_, t.isym, t.ictx, t.iunl, t.ienc, t.irob,
                                     t.ial});
+        apply_item_patches(kIpAtItems, t, nitems);
         const uint32_t nchunks = (nitems + kChunkItems - 1) / kChunkItems;
         if (nchunks > kMaxChunks) throw std::runtime_error("too many chunks in a block");
         if (stream_start_) {  // src/lz.rs:238-265
@@ -1605,6 +1608,7 @@ class StreamEncoder {
         if (h.fail == kOutFull) throw std::runtime_error("the output buffer is too small for the stream (block " + std::to_string(h.fail_block) + ")");
         if (h.fail == kOutChunk) throw std::runtime_error("chunk payload overflow");
         if (fast_ && stats.blocks && verify_mode() == 2) report_verify("stream");
+        check_item_patches();
         stats.out_bytes = (uint64_t)h.off;
         return DeviceResult{dout_, (size_t)h.off};
     }
@@ -1613,6 +1617,7 @@ class StreamEncoder {
         collect(out, nullptr);
         stats.host_syncs += be_.take_host_syncs();
         if (fast_ && stats.blocks && verify_mode() == 2) report_verify("stream");
+        check_item_patches();
     }
     static int verify_mode() {  // FastVerify (diagnostics of the fast parse; the gate below is what guards the output)
         static const int m = getenv("ORZ_FAST_VERIFY") ? atoi(getenv("ORZ_FAST_VERIFY")) : 0;
@@ -1633,6 +1638,62 @@ class StreamEncoder {
         msg += " first at window offset " + std::to_string(e[kVeFirst] - 1) + " -- the encode fails, nothing of this block is handed out (a streaming call has written the blocks before it: its output is incomplete)";
         fprintf(stderr, "orz: %s\n", msg.c_str());
         throw std::runtime_error(msg);
+    }
+    // (tests of the gate) item patches, see orz_verify.h: the list holds for the NEXT stream only -- whoever runs that stream calls
+    // clear_item_patches() on every path out of it.  Throws std::invalid_argument, before anything reaches the device, for a value a
+    // later kernel would index with out of range: the per-position arrays hold kWLen entries and a source is read below its item
+    // (SRC in [1, pos)); ML sizes the byte comparison (<= 240); symbol, context, flag and length code index the ranking, the
+    // histograms and the Huffman tables (389 / 512 / 2 / 240); the offset bits are packed by their own count (<= 12 bits, none above
+    // it).  A literal or WORD has no source on record, so no patch may call one a match.
+    static constexpr size_t kMaxItemPatches = 1u << 16;
+    void set_item_patches(const ItemPatch* list, size_t n) {
+        if (n > kMaxItemPatches || (n && !list)) throw std::invalid_argument("item patches: at most 65536 patches, and a list to read them from");
+        for (size_t i = 0; i < n; i++) {
+            const ItemPatch& q = list[i];
+            const uint32_t v = q.value;
+            bool ok = q.field < kIpFields && q.pos >= kPre && q.pos < kPre + kNewMax;
+            switch (q.field) {
+                case kIpType: ok = ok && v < kTyMatch; break;
+                case kIpLen: ok = ok && v <= kMaxLen; break;
+                case kIpSrc: ok = ok && v >= 1 && v < q.pos; break;
+                case kIpSym: ok = ok && v < kSyms; break;
+                case kIpCtx: ok = ok && v < 512; break;
+                case kIpAl: ok = ok && v <= 1; break;
+                case kIpEnc: ok = ok && v < kLenSyms; break;
+                case kIpRob: ok = ok && (v >> 12) <= 12 && ((v & 0xfff) >> (v >> 12)) == 0; break;
+                case kIpUnl: ok = ok && v < 256; break;
+                case kIpLmv: ok = ok && v <= 127; break;
+                default: break;  // (ORD: any value -- it is compared, never used as an index, once ItemSyms has run)
+            }
+            if (!ok) throw std::invalid_argument("item patches: patch " + std::to_string(i) + " (field " + std::to_string(q.field) + ", value " + std::to_string(v) +
+                                                 ") is outside the range the later kernels index with");
+        }
+        if (n && !ipatch_) {
+            ipatch_ = take<ItemPatch>(kMaxItemPatches);
+            ipatch_applied_ = take<uint32_t>(1);
+        }
+        npatch_ = (uint32_t)n;
+        if (!n) return;
+        be_.h2d(ipatch_, list, n * sizeof(ItemPatch));
+        be_.memset(ipatch_applied_, 0, 4);
+        fprintf(stderr, "orz: WARNING: the test hook %s is set in the environment: this encoder DELIBERATELY DAMAGES what it encodes "
+                        "(its streams are invalid unless a guard catches the damage); unset it for real use\n", "orz_stream_set_item_patches");
+    }
+    void clear_item_patches() { npatch_ = 0; }
+    template <class TS>
+    void apply_item_patches(uint32_t point, TS& t, uint32_t nitems) {
+        if (!npatch_) return;
+        be_.launch(npatch_, ItemPatchApply{ipatch_, npatch_, (uint32_t)stats.blocks, point, t.ipos, nitems, TY_, ML_, LMV_, SRC_, ORD_,
+                                           t.isym, t.ictx, t.irob, t.iunl, t.ienc, t.ial, ipatch_applied_});
+    }
+    // a patch that found no item start at its (block, position) tested nothing: the stream is not handed out
+    void check_item_patches() {
+        if (!npatch_) return;
+        uint32_t applied = 0;
+        be_.d2h(&applied, ipatch_applied_, 4);
+        if (applied != npatch_)
+            throw std::runtime_error("item patches: " + std::to_string(npatch_ - applied) + " of " + std::to_string(npatch_) +
+                                     " patches were not applied (no item starts at their block and position): the encode fails");
     }
     // (tests) damage the n-th suitable item of every block after the parse: "hole", "context", "ring", "lenmin", "word", "bytes"
     void set_inject(uint32_t kind, uint32_t nth) { inject_kind_ = kind; inject_nth_ = nth; }
@@ -1865,6 +1926,9 @@ class StreamEncoder {
     uint32_t *vrec_ = nullptr, *vord_ = nullptr, *vctx_ = nullptr, *vlast_ = nullptr;  // the gate's decoder state (orz_verify.h)
     uint8_t* vwords_ = nullptr;
     uint32_t inject_kind_ = 0, inject_nth_ = 0;
+    ItemPatch* ipatch_ = nullptr;  // (tests of the gate) the patch list of the next stream, and how many of its patches found their item
+    uint32_t* ipatch_applied_ = nullptr;
+    uint32_t npatch_ = 0;
     size_t out_inject_ = 0;  // byte of the stream's first chunk whose lowest bit is flipped on its way out (0 = none)
     uint16_t* srbackup_ = nullptr;  // the tables before the running block's ranking (the guard's second run starts from them)
     uint64_t* outoff_;

@@ -379,4 +379,58 @@ struct VerInjectK {
     }
 };
 
+// Item patches for the gate's tests (orz_stream_set_item_patches): where the injections above damage "the n-th suitable item of
+// every block", a patch names its item -- (block counter of the item trace, window offset of the item start) -- and the field it
+// overwrites, so a test can aim at the first and the last item of a unit, at a unit behind a slide, and at LEGAL parses the
+// parser never writes (another source of the same ring).  Three points of the post stage, one launch each, a thread per patch:
+//   kIpAtParse   TYPE / LEN / SRC in the per-position arrays, where VerInjectK runs (before LenMinKeys: the len_min bookkeeping
+//                and ItemSyms see the patched parse, as they would a parse defect -- or another legal parse)
+//   kIpAtLenMin  LMV, where VerInjectLmv runs
+//   kIpAtItems   SYM / CTX / AL / ENC / ROB / UNL in the item arrays right after ItemSyms (before the census and the sort by
+//                context: a damaged context is ranked where it says), ORD in the parse's ordinals
+// A patch whose position is no item start of its block is left alone; `applied` counts the others, the host compares.  The host
+// has refused every value a later kernel would index with out of range (StreamEncoder::set_item_patches).
+enum ItemPatchField : uint32_t { kIpType = 0, kIpLen, kIpSrc, kIpSym, kIpCtx, kIpAl, kIpEnc, kIpRob, kIpUnl, kIpOrd, kIpLmv, kIpFields };
+enum ItemPatchPoint : uint32_t { kIpAtParse = 0, kIpAtLenMin, kIpAtItems };
+struct ItemPatch { uint32_t block, pos, field, value; };
+ORZ_HD uint32_t item_patch_point(uint32_t field) { return field <= kIpSrc ? kIpAtParse : (field == kIpLmv ? kIpAtLenMin : kIpAtItems); }
+struct ItemPatchApply {
+    const ItemPatch* list;
+    uint32_t n, block, point;
+    const uint32_t* ipos;
+    uint32_t nitems;
+    uint8_t *TY, *ML, *LMV;
+    uint32_t *SRC, *ORD;
+    uint16_t *isym, *ictx, *irob;
+    uint8_t *iunl, *ienc, *ial;
+    uint32_t* applied;
+    ORZ_HD void operator()(size_t t) const {
+        if (t >= n) return;
+        const ItemPatch pt = list[t];
+        if (pt.block != block || pt.field >= kIpFields || item_patch_point(pt.field) != point) return;
+        uint32_t lo = 0, hi = nitems;  // the item that starts at pt.pos, if any
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (ipos[mid] < pt.pos) lo = mid + 1; else hi = mid;
+        }
+        if (lo >= nitems || ipos[lo] != pt.pos) return;
+        const uint32_t k = lo, p = pt.pos, v = pt.value;
+        switch (pt.field) {
+            case kIpType: TY[p] = (uint8_t)((TY[p] & ~3u) | (v & 3)); break;
+            case kIpLen: ML[p] = (uint8_t)v; break;
+            case kIpSrc: SRC[p] = v; break;
+            case kIpLmv: LMV[p] = (uint8_t)v; break;
+            case kIpSym: isym[k] = (uint16_t)v; break;
+            case kIpCtx: ictx[k] = (uint16_t)v; break;
+            case kIpAl: ial[k] = (uint8_t)((ial[k] & ~1u) | (v & 1)); break;
+            case kIpEnc: ienc[k] = (uint8_t)v; break;
+            case kIpRob: irob[k] = (uint16_t)v; break;
+            case kIpUnl: iunl[k] = (uint8_t)v; break;
+            case kIpOrd: ORD[p] = v; break;
+            default: break;
+        }
+        ORZ_ATOMIC_ADD(applied, 1u);
+    }
+};
+
 }  // namespace orz

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 
@@ -422,6 +423,59 @@ extern "C" long emu_encode_fast_trace(const uint8_t* src, size_t n, int depth, i
         return (long)tr.pos.size();
     } catch (const std::exception& e) {
         std::fprintf(stderr, "emu_encode_fast_trace: %s\n", e.what());
+        return -1;
+    }
+}
+// orz_stream_set_item_patches + orz_stream_encode on the emulation backend (tests of the validity gate): `src` through an encoder
+// that is KEPT from call to call while the settings (level, mode, ORZ_FAST_UNIT) stay the same and `fresh` is 0 -- a sweep of
+// patched encodes shares one, as a caller of the library would after a finding.  Returns the number of items of the stream (up
+// to `cap` of them in `items`) and the stream; -1 with the message in `err` when the encode fails; -2 with the message when the
+// patch list is refused.  The list holds for this call only.
+struct EmuGateItem { uint32_t block, pos, src; uint16_t sym, ctx, rob, pad; uint8_t mlen, al, unl, enc; };
+extern "C" long emu_encode_fast_patched(const uint8_t* src, size_t n, int depth, int lazy1, int lazy2, int exact, int fresh,
+                                        const orz::ItemPatch* patches, size_t npatches, uint8_t** dst, size_t* dst_len, EmuGateItem* items,
+                                        size_t cap, char* err, size_t errcap) {
+    struct Kept {
+        std::string key;
+        std::unique_ptr<EmuBackend> be;
+        std::unique_ptr<orz::StreamEncoder<EmuBackend>> enc;
+    };
+    static Kept kept;
+    try {
+        const char* unit = std::getenv("ORZ_FAST_UNIT");
+        const std::string key = std::to_string(depth) + "," + std::to_string(lazy1) + "," + std::to_string(lazy2) + "," + std::to_string(exact) + "," + (unit ? unit : "");
+        if (fresh || !kept.enc || kept.key != key) {
+            kept.enc.reset();
+            kept.be.reset(new EmuBackend);
+            orz::Cfg cfg{depth, lazy1, lazy2};
+            if (exact) kept.enc.reset(new orz::StreamEncoder<EmuBackend>(*kept.be, cfg, 62, 256));
+            else kept.enc.reset(new orz::StreamEncoder<EmuBackend>(*kept.be, cfg, 62, 64, true, orz::kFastTile, orz::kFastRounds));
+            kept.key = key;
+        }
+        orz::StreamEncoder<EmuBackend>& enc = *kept.enc;
+        try {
+            enc.set_item_patches(patches, npatches);
+        } catch (const std::invalid_argument& e) {
+            put_err(e, err, errcap);
+            return -2;
+        }
+        struct Clear {
+            orz::StreamEncoder<EmuBackend>& e;
+            ~Clear() { e.clear_item_patches(); e.trace = nullptr; }
+        } clear{enc};
+        orz::ItemTrace tr;
+        enc.trace = &tr;
+        std::vector<uint8_t> out;
+        orz::encode_stream(enc, *kept.be, src, n, false, out);
+        *dst = (uint8_t*)std::malloc(out.size() ? out.size() : 1);
+        std::memcpy(*dst, out.data(), out.size());
+        *dst_len = out.size();
+        const size_t k = tr.pos.size() < cap ? tr.pos.size() : cap;
+        for (size_t i = 0; i < k; i++)
+            items[i] = EmuGateItem{tr.block[i], tr.pos[i], tr.src[i], tr.sym[i], tr.ctx[i], tr.rob[i], 0, tr.mlen[i], tr.al[i], tr.unl[i], tr.enc[i]};
+        return (long)tr.pos.size();
+    } catch (const std::exception& e) {
+        put_err(e, err, errcap);
         return -1;
     }
 }
