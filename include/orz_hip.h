@@ -450,6 +450,33 @@ int orz_huffman_tables(int device, const uint32_t* weights, size_t nchunks, uint
 int orz_symrank_chains(int device, uint16_t* tables, const uint32_t* gsym, const uint32_t* rstart, size_t nitems,
                        uint16_t* ranks, uint32_t* flags2, double* elapsed_us);
 
+/* FOR TESTS: the step machinery of the fast parse's round loop (orz_fast.h) run once on host arrays -- no stream object, no
+ * encode; the launches are the product's own (orz_fast_step.h).  Arrays that a kernel writes are in/out: the caller pre-fills
+ * them and gets them back whole, so what a kernel leaves alone comes back as it went in.  With nsub = ceil(n / 4096) and
+ * ntile = ceil(n / tile), in entries: wbytes n + 2 (window offsets SBVEC_PREMATCH_LEN - 2 .. window end), ev n + 520, ty / nl /
+ * x0 / pt n + 4608, x1 (nsub + 2) * 240, x2 (ntile + 2) * 240, centry nsub + 2, tentry ntile + 2, sbits n / 64 + 16, cm
+ * (nsub + 2) * 256.
+ * orz_fast_step_path: the path stage of one step over the tiles t_lo .. t_hi, the path entering at window offset `entry`
+ * (tentry[t_lo]).  form 0: PathUpWave deciding, with a FastRetireDone part of zero positions; 1: FastDecide, then PathUpWave;
+ * 2: the thread-per-item forms (FastDecide, PathSeg, PathChunk, PathTileDown, PathMark, CountWave); 0 and 1 go on with
+ * PathTileDown and PathMarkWave.  lds_bytes, when not NULL, receives PathTileDown's LDS need (0 = the global-memory walk).
+ * ORZ_EINVAL, before anything reaches the device, for a length field of ev[0 .. n) that is neither 0 nor 4 .. 240, an entry
+ * outside [lo, lo + 240), a tile that is not a multiple of 4096, tiles outside the block.
+ * orz_fast_step_counts: count != 0: CountWave over all subtiles (cm from sbits), else cm as given ([rows][256]); FastPrefix
+ * {s0, s1, ext, cpt, live_end} alone into cp and as the prefix half of FlipPrefixWave (no positions to flip) into cp2
+ * ([rows + 1][256] each, row s0 given); FastItemTotal over cp into acc2 (acc, hotacc); OrdWave into ord and OrdWave2 into ord2
+ * (n entries each), both from cp.
+ * orz_fast_step_horizon: FastHorizon over the subtiles s0 .. s1 alone into hz and as the horizon half of RetireHorizonWave (no
+ * retiring positions) into hz2 ([s1 + 1][256][4] each); cp [rows][256] with rows >= s1 + 2, hpre [4097][256]. */
+int orz_fast_step_path(int device, unsigned form, uint32_t n, uint32_t tile, uint32_t t_lo, uint32_t t_hi, uint32_t entry,
+                       const uint8_t* wbytes, const uint32_t* ev, uint8_t* ty, uint8_t* nl, uint8_t* x0, uint8_t* x1, uint8_t* x2,
+                       uint32_t* centry, uint32_t* tentry, uint64_t* sbits, uint8_t* pt, uint32_t* cm, uint64_t* lds_bytes);
+int orz_fast_step_counts(int device, uint32_t n, const uint8_t* wbytes, const uint64_t* sbits, int count, uint32_t s0, uint32_t s1,
+                         uint32_t ext, uint32_t cpt, uint32_t live_end, uint32_t rows, uint32_t* cm, uint32_t* cp, uint32_t* cp2,
+                         uint32_t* ord, uint32_t* ord2, uint32_t* acc2);
+int orz_fast_step_horizon(int device, const uint32_t* cp, uint32_t rows, const uint32_t* hpre, uint32_t s0, uint32_t s1, uint32_t* hz,
+                          uint32_t* hz2);
+
 int orz_device_count(void);
 const char* orz_last_error(void);
 const char* orz_version(void);

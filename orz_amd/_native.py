@@ -275,6 +275,21 @@ SYMBOLS = [
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.POINTER(ctypes.c_double)],
     ),
+    (
+        "orz_fast_step_path",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_uint] + [ctypes.c_uint32] * 5 + [ctypes.c_void_p] * 12 + [ctypes.POINTER(ctypes.c_uint64)],
+    ),
+    (
+        "orz_fast_step_counts",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.c_void_p] * 6,
+    ),
+    (
+        "orz_fast_step_horizon",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     ("orz_device_count", ctypes.c_int, []),
     ("orz_last_error", ctypes.c_char_p, []),
     ("orz_version", ctypes.c_char_p, []),

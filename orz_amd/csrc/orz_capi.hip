@@ -23,6 +23,7 @@
 #include "orz_planes.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
+#include "orz_fast_step.h"
 
 namespace {
 // An encoder drives three HIP streams (parse; symbol ranking; Huffman + packing) and the members interface runs several
@@ -1102,6 +1103,40 @@ int orz_huffman_tables(int device, const uint32_t* weights, size_t nchunks, uint
     } catch (const std::exception& e) {
         return fail(ORZ_EINVAL, e.what());
     }
+}
+
+// ------------------------------------------------------------------------------ the fast parse's step machinery alone
+int orz_fast_step_path(int device, unsigned form, uint32_t n, uint32_t tile, uint32_t t_lo, uint32_t t_hi, uint32_t entry,
+                       const uint8_t* wbytes, const uint32_t* ev, uint8_t* ty, uint8_t* nl, uint8_t* x0, uint8_t* x1, uint8_t* x2,
+                       uint32_t* centry, uint32_t* tentry, uint64_t* sbits, uint8_t* pt, uint32_t* cm, uint64_t* lds_bytes) {
+    const int bad = mapped([&] { orz::fast_step_path_check(form, n, tile, t_lo, t_hi, entry, wbytes, ev, ty, nl, x0, x1, x2, centry, tentry, sbits, pt, cm); });
+    if (bad) return bad;
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    return mapped([&] {
+        orz::HipBackend be(device);
+        orz::fast_step_path(be, form, n, tile, t_lo, t_hi, entry, wbytes, ev, ty, nl, x0, x1, x2, centry, tentry, sbits, pt, cm, lds_bytes);
+    });
+}
+int orz_fast_step_counts(int device, uint32_t n, const uint8_t* wbytes, const uint64_t* sbits, int count, uint32_t s0, uint32_t s1,
+                         uint32_t ext, uint32_t cpt, uint32_t live_end, uint32_t rows, uint32_t* cm, uint32_t* cp, uint32_t* cp2,
+                         uint32_t* ord, uint32_t* ord2, uint32_t* acc2) {
+    const int bad = mapped([&] { orz::fast_step_counts_check(n, wbytes, sbits, s0, s1, ext, cpt, live_end, rows, cm, cp, cp2, ord, ord2, acc2); });
+    if (bad) return bad;
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    return mapped([&] {
+        orz::HipBackend be(device);
+        orz::fast_step_counts(be, n, wbytes, sbits, count, s0, s1, ext, cpt, live_end, rows, cm, cp, cp2, ord, ord2, acc2);
+    });
+}
+int orz_fast_step_horizon(int device, const uint32_t* cp, uint32_t rows, const uint32_t* hpre, uint32_t s0, uint32_t s1, uint32_t* hz,
+                          uint32_t* hz2) {
+    const int bad = mapped([&] { orz::fast_step_horizon_check(cp, rows, hpre, s0, s1, hz, hz2); });
+    if (bad) return bad;
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    return mapped([&] {
+        orz::HipBackend be(device);
+        orz::fast_step_horizon(be, cp, rows, hpre, s0, s1, hz, hz2);
+    });
 }
 
 // ------------------------------------------------------------------------------ symbol ranking alone

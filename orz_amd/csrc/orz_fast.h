@@ -1665,6 +1665,54 @@ struct RetireHorizonWave {
     }
 };
 
+// ---- the path stage of a step: its launches in ONE place (the round loop of StreamEncoder::fast_parse and the stand-alone
+// test entry points of orz_fast_step.h both call this, so the grids below are stated once) ------------------------------------
+// The range of a step: tiles t_lo .. t_hi of a.tile positions, window offsets [lo, hi), chunks c0 .. c0 + nc - 1.
+struct PathRange { uint32_t lo, hi, c0, nc, nt; };
+ORZ_HD PathRange path_range(const FastArgs& a, uint32_t t_lo, uint32_t t_hi) {
+    PathRange r;
+    r.lo = kPre + t_lo * a.tile;
+    const uint64_t end = (uint64_t)kPre + (uint64_t)(t_hi + 1) * a.tile;
+    r.hi = (uint32_t)(a.len < end ? a.len : end);
+    r.c0 = t_lo * (a.tile / kSub);
+    r.nc = (r.hi - (kPre + r.c0 * kSub) + kSub - 1) / kSub;
+    r.nt = t_hi - t_lo + 1;
+    return r;
+}
+// kPathFused: ONE launch decides, draws up the chunk maps and folds the counters of the tile that retired in the step before
+// (`done`; done.lo == done.hi: none).  kPathUnfused: FastDecide, then PathUpWave from a.nl (ORZ_FAST_FUSED=0; `done` is the
+// caller's business then).  kPathPlain: the thread-per-item forms of every map, the readable statement of the same work --
+// launched by the tests only (`done` unused).  From decisions to marks: ty, nl, x0, x1, x2, centry, tentry, sbits, pt, cm.
+enum PathForm : uint32_t { kPathFused = 0, kPathUnfused = 1, kPathPlain = 2 };
+template <class BE>
+PathRange fast_path_stage(BE& be, const FastArgs& a, uint32_t t_lo, uint32_t t_hi, PathForm form, const FastRetireDone& done) {
+    const PathRange r = path_range(a, t_lo, t_hi);
+    const uint32_t lo = r.lo, hi = r.hi, c0 = r.c0, nc = r.nc;
+    be.timed_begin(3);
+    if (form == kPathFused) {
+        PathUpWave up{a, c0};
+        up.decide = 1; up.nup = nc * 4; up.done = done;
+        be.launch_waves((size_t)nc * 4 + (done.hi - done.lo + 63) / 64, up, PathUpWave::lds_bytes());
+    } else {
+        be.launch(hi - lo, FastDecide{a, lo, hi});
+        if (form == kPathUnfused) {
+            be.launch_waves((size_t)nc * 4, PathUpWave{a, c0}, PathUpWave::lds_bytes());
+        } else {
+            be.launch(hi - lo, PathSeg{a, lo, hi});
+            be.launch((size_t)nc * kEntries, PathChunk{a, c0, nc});
+        }
+    }
+    be.timed_end(3);
+    be.launch_group(PathTileDown{a, t_lo, r.nt});
+    if (form == kPathPlain) {
+        be.launch((hi - lo + kSeg64 - 1) / kSeg64, PathMark{a, (lo - kPre) / kSeg64, (hi - lo + kSeg64 - 1) / kSeg64});
+        be.launch_waves(nc, CountWave{a, c0}, CountWave::lds_bytes());
+    } else {
+        be.launch_waves(nc, PathMarkWave{a, c0}, PathMarkWave::lds_bytes());
+    }
+    return r;
+}
+
 // ---- after the rounds: sources, repairs, exact predictor ---------------------------------------------
 // The repair passes run without the host in the loop: every kernel of a pass returns at once when an earlier pass found
 // nothing to repair (`done`), FastPassEnd closes a pass on the device, and the host reads this block once per group of
