@@ -135,7 +135,8 @@ long orz_stream_get_kernel_table(orz_stream*, orz_kernel_row* rows, size_t cap);
 /* tuning: bytes per speculative segment and segments per sweep window (0 = keep) */
 int orz_stream_set_tuning(orz_stream*, unsigned seg_bytes, unsigned window_segs);
 /* Encode `n` bytes at `src` (host memory, or device memory when src_on_device != 0) into a
- * malloc()ed orz stream (*dst, free with orz_free).  Same bytes as `orz encode` would write. */
+ * library-owned orz stream (*dst, release with orz_free and nothing else: results of 1 MiB or more are page-locked buffers of
+ * a small pool that orz_free hands back to it).  Same bytes as `orz encode` would write. */
 int orz_stream_encode(orz_stream*, const void* src, size_t n, int src_on_device, uint8_t** dst, size_t* dst_len,
                       orz_encode_stats* stats);
 void orz_free(void* p);

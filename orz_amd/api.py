@@ -35,7 +35,7 @@ def stream_bound(nbytes):
 
 
 class OrzBuffer:
-    """A stream the library returned (malloc'ed by orz_stream_encode), held without copying; freed with orz_free."""
+    """A stream the library returned (orz_stream_encode's own buffer), held without copying; released with orz_free."""
 
     def __init__(self, lib, ptr, n):
         self._lib, self._ptr, self._n = lib, ptr, int(n)

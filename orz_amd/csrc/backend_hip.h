@@ -686,7 +686,7 @@ class HipBackend {
         launch(nw, SymGuardBegin{reinterpret_cast<const uint64_t*>(srstate), reinterpret_cast<uint64_t*>(backup), nw, flags});
         Bracket br(*this, profile_ ? KernelNames::lib("orz_symrank_kernel (+ guard)") : 0);
         timed_begin(1);
-        hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(64), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)nullptr,
+        hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(kSrThreads), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)nullptr,
                            (const uint32_t*)nullptr);
         ORZ_HIP_CHECK(hipGetLastError());
         timed_end(1);
@@ -694,14 +694,14 @@ class HipBackend {
         const long inject = inj ? atol(inj) : -1;
         if (inject >= 0 && (uint32_t)inject < nitems) launch(1, SymInject{gsym, grank, (uint32_t)inject});
         launch(SymCheck::kThreads, SymCheck{gsym, grank, nitems, flags, nullptr});
-        hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(64), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)backup,
+        hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(kSrThreads), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)backup,
                            (const uint32_t*)flags);
         ORZ_HIP_CHECK(hipGetLastError());
         launch(SymCheck::kThreads, SymCheck{gsym, grank, nitems, flags + 1, flags});
         static const bool verify = getenv("ORZ_SYMRANK_VERIFY") && atoi(getenv("ORZ_SYMRANK_VERIFY"));
         if (verify && keep) {
             launch(SymCompare::kThreads, SymKeep{grank, keep, nitems});
-            hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(64), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)backup,
+            hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(kSrThreads), 0, stream_, srstate, gsym, grank, rstart, (const uint16_t*)backup,
                                (const uint32_t*)nullptr);
             ORZ_HIP_CHECK(hipGetLastError());
             launch(SymCompare::kThreads, SymCompare{grank, keep, nitems, flags + 2});

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <atomic>
@@ -121,6 +122,85 @@ unsigned window_for(const orz::HipBackend& be, const orz_lzcfg& c, unsigned aske
 
 }  // namespace
 
+// ---- the results of orz_stream_encode: page-locked host buffers from a small process-wide pool.
+// A stream's bytes used to come to the host by a blocking copy into freshly malloc'ed (pageable, untouched) memory after the
+// last kernel of every call: 5.5 ms for the 28 MB of the 100 MB text workload, 0.6 ms into a page-locked buffer.
+// Allocating a page-locked buffer costs more than the copy, so buffers are kept:
+// a capacity is a power of two (a caller's streams of similar size reuse each other's buffers), at most two idle buffers wait
+// for the next call, and the idle ones are released with the last stream handle.  Results under 1 MiB stay malloc'ed.
+namespace {
+constexpr size_t kPoolMin = size_t(1) << 20;
+constexpr size_t kPoolIdleMax = 2;
+struct ResultPool {
+    std::mutex mu;
+    std::map<void*, size_t> out;                  // handed to callers: pointer -> capacity
+    std::vector<std::pair<void*, size_t>> idle;   // waiting for the next call
+    size_t handles = 0;                           // live orz_stream handles
+    static size_t capacity_for(size_t n) {
+        size_t c = kPoolMin;
+        while (c < n) c <<= 1;
+        return c;
+    }
+    // a buffer of n bytes or more; nullptr when page-locked memory cannot be had (the caller falls back to malloc)
+    void* take(size_t n) {
+        const size_t cap = capacity_for(n);
+        {
+            std::lock_guard<std::mutex> g(mu);
+            size_t best = idle.size();
+            for (size_t i = 0; i < idle.size(); i++)
+                if (idle[i].second >= cap && (best == idle.size() || idle[i].second < idle[best].second)) best = i;
+            if (best < idle.size()) {
+                void* p = idle[best].first;
+                out[p] = idle[best].second;
+                idle.erase(idle.begin() + (long)best);
+                return p;
+            }
+        }
+        void* p = nullptr;
+        if (hipHostMalloc(&p, cap, hipHostMallocPortable) != hipSuccess || !p) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        std::lock_guard<std::mutex> g(mu);
+        out[p] = cap;
+        return p;
+    }
+    // true: p was a pool buffer and is taken back (kept idle, or released when two wait already or no stream is left)
+    bool give(void* p) {
+        size_t cap = 0;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            auto it = out.find(p);
+            if (it == out.end()) return false;
+            cap = it->second;
+            out.erase(it);
+            if (handles > 0 && idle.size() < kPoolIdleMax) {
+                idle.emplace_back(p, cap);
+                return true;
+            }
+        }
+        (void)hipHostFree(p);
+        return true;
+    }
+    void handle_born() {
+        std::lock_guard<std::mutex> g(mu);
+        handles++;
+    }
+    void handle_gone() {
+        std::vector<std::pair<void*, size_t>> drop;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (handles > 0 && --handles == 0) drop.swap(idle);
+        }
+        for (auto& b : drop) (void)hipHostFree(b.first);
+    }
+};
+ResultPool& result_pool() {
+    static ResultPool* const pool = new ResultPool;  // (never destroyed: orz_free may run during process teardown)
+    return *pool;
+}
+}  // namespace
+
 struct orz_stream {
     std::unique_ptr<orz::HipBackend> be;
     std::unique_ptr<Enc> enc;
@@ -212,7 +292,10 @@ int orz_lzcfg_from_level(int level, orz_lzcfg* out) {  // src/main.rs:97-102
     }
 }
 
-void orz_free(void* p) { std::free(p); }
+void orz_free(void* p) {
+    if (!p) return;
+    if (!result_pool().give(p)) std::free(p);
+}
 
 // ------------------------------------------------------------------------------ orz_stream
 static orz_stream* stream_new(int device, const orz_lzcfg* cfg, bool lone) {
@@ -231,6 +314,7 @@ static orz_stream* stream_new(int device, const orz_lzcfg* cfg, bool lone) {
         s->be->set_graphs(env_u("ORZ_GRAPHS", 1) != 0);
         if (!lone) s->unit = orz::kNewMax;  // one of several encoders on the device: whole blocks (orz_stream.h, unit_)
         s->rebuild();
+        result_pool().handle_born();
         return s.release();
     } catch (const std::exception& e) {
         fail(ORZ_ENODEV, e.what());
@@ -243,6 +327,7 @@ void orz_stream_free(orz_stream* s) {
     s->enc.reset();
     s->be.reset();
     delete s;
+    result_pool().handle_gone();
 }
 int orz_stream_set_tuning(orz_stream* s, unsigned seg_bytes, unsigned window_segs) {
     if (!s) return fail(ORZ_EINVAL, "null stream");
@@ -360,14 +445,17 @@ int orz_stream_encode(orz_stream* s, const void* src, size_t n, int src_on_devic
     if (!s->enc) return fail(ORZ_ENOMEM, "the stream has no encoder (a reconfiguration ran out of device memory)");
     try {
         const auto r = stream_encode_device(s, src, n, src_on_device, nullptr, 0, stats);
-        // the finished stream comes to the host in ONE copy (round 6; before: a wait for the sizes and one for the bytes of every block)
-        uint8_t* p = (uint8_t*)std::malloc(r.len ? r.len : 1);
+        // the finished stream comes to the host in ONE copy (round 6; before: a wait for the sizes and one for the bytes of every
+        // block) -- into a page-locked buffer of the result pool when it is 1 MiB or more
+        uint8_t* p = r.len >= kPoolMin ? (uint8_t*)result_pool().take(r.len) : nullptr;
+        if (!p) p = (uint8_t*)std::malloc(r.len ? r.len : 1);
         if (!p) return fail(ORZ_ENOMEM, "out of host memory");
-        const hipError_t ce = hipMemcpy(p, r.data, r.len, hipMemcpyDeviceToHost);
+        hipError_t ce = hipMemcpyAsync(p, r.data, r.len, hipMemcpyDeviceToHost, s->be->stream());
+        if (ce == hipSuccess) ce = hipStreamSynchronize(s->be->stream());
         if (stats) stats->host_syncs += 1;
-        if (ce != hipSuccess) { std::free(p); return fail(ORZ_ENODEV, hipGetErrorString(ce)); }
+        if (ce != hipSuccess) { orz_free(p); return fail(ORZ_ENODEV, hipGetErrorString(ce)); }
         if (verify_decode_on()) {
-            try { verify_stream_decode((const uint8_t*)src, n, src_on_device != 0, p, r.len); } catch (...) { std::free(p); throw; }
+            try { verify_stream_decode((const uint8_t*)src, n, src_on_device != 0, p, r.len); } catch (...) { orz_free(p); throw; }
         }
         *dst_len = r.len;
         *dst = p;

@@ -29,7 +29,7 @@ int main(int argc, char** argv) {
             hipMemset(dk, 0xee, n * 2);
             hipEventRecord(a);
             if (which == 0) hipLaunchKernelGGL(orz_symrank_kernel_r3, dim3(512), dim3(64), 0, 0, ds, dg, dk, dr, (const uint16_t*)nullptr, (const uint32_t*)nullptr);
-            else hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(64), 0, 0, ds, dg, dk, dr, (const uint16_t*)nullptr, (const uint32_t*)nullptr);
+            else hipLaunchKernelGGL(orz_symrank_kernel, dim3(512), dim3(kSrThreads), 0, 0, ds, dg, dk, dr, (const uint16_t*)nullptr, (const uint32_t*)nullptr);
             hipEventRecord(b); hipEventSynchronize(b);
             float ms; hipEventElapsedTime(&ms, a, b); if (ms < best) best = ms;
         }
