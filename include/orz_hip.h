@@ -201,6 +201,26 @@ int orz_stream_set_item_patches(orz_stream*, const orz_item_patch* patches, size
  * table has, no captured block. */
 long orz_stream_fast_tables(orz_stream*, int arm_block, const char* name, void* dst, size_t cap);
 
+/* FOR TESTS: the repair stage of one block of the fast parse (orz_fast.h: RepairListWave, FastSource, FastRecut, FastWordCheckL,
+ * FastWordApplyL, ...), pass by pass.  orz_stream_arm_repair_probe arms it for the `block`-th encode_block call of the NEXT encode
+ * on this stream (block < 0 disarms).  The armed block runs its rounds and repair passes outside the captured graph -- the same
+ * launches in the same order -- and waits before every FastPassEnd to copy the state to host memory; the stream is the one an
+ * unarmed encode writes, and an unarmed encode does nothing for this.  ty / nl (n bytes each, or NULL / NULL / 0): a decision
+ * field for every position of the armed block, on and off the path, that replaces the rounds' before the first pass: ty = 0 WORD,
+ * 1 literal, 2 match; nl = 0 (undecided: read as a literal), 1 for a literal, 2 for WORD, 4..240 for a match; i + nl[i] <= n.
+ * The path (walked from the block's first position) and the previous-item types follow from it; n must be the armed block's size
+ * (else that encode returns ORZ_EINVAL when it reaches the block, before the block is parsed).  orz_stream_repair_probe: the size in bytes of a table of the probed block, of which up to `cap` bytes
+ * are copied to dst.  Tables: "scalars" (eight u64: n, K, depth, block number, sizeof the control block, 1 in the lists form, 0, 0), "passes" (u32:
+ * passes recorded, the last of which repaired nothing), "before.ty|nl|pt" (n + 1 bytes), "before.sbits" (u64 words), per pass k
+ * "p<k>.ty|nl|pt|sbits", "p<k>.src" (n u32: window offsets), "p<k>.edge" (n bytes), "p<k>.cok" (512 u32: the per-context counters
+ * and flags), "p<k>.ctl" (the control block as the pass left it: u32 chg, done, total, passes, nmem, acc, lt, lastflips, nent,
+ * ncut, nfix, nwx, hot, hotacc), lists form: "p<k>.mcnt|wcnt" (entries per subtile) and "p<k>.mlist|wlist" (u16 rows of 1024 / 2048
+ * entries, one row more than the block has subtiles; the rows are filled with 0xa5 before the first pass of the armed block), and
+ * "final.S|TY|ML|W0" (n bytes), "final.ctl", lists form: "final.items" (u32).  ORZ_EINVAL, before anything reaches the device: an exact-mode stream, a block number above 65535, a field that
+ * breaks the contract, a name that no table has, no probed block. */
+int orz_stream_arm_repair_probe(orz_stream*, int block, const unsigned char* ty, const unsigned char* nl, size_t n);
+long orz_stream_repair_probe(orz_stream*, const char* name, void* dst, size_t cap);
+
 /* ---- many members per GPU (independent chunks, each a complete orz stream) ------------
  * A stream does not shard (its model state is one adaptive chain), so throughput beyond one stream
  * comes from encoding independent members concurrently: `jobs` stream encoders on one device, each fed

@@ -263,6 +263,8 @@ SYMBOLS = [
     ("orz_stream_get_item_trace", ctypes.c_long, [ctypes.c_void_p, ctypes.POINTER(Item), ctypes.c_size_t]),
     ("orz_stream_set_item_patches", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("orz_stream_fast_tables", ctypes.c_long, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]),
+    ("orz_stream_arm_repair_probe", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    ("orz_stream_repair_probe", ctypes.c_long, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("orz_huffman_stride", ctypes.c_size_t, []),
     (
         "orz_huffman_tables",

@@ -214,6 +214,32 @@ class StreamEncoder:
             out[name] = get(name, dtype)
         return out
 
+    def arm_repair_probe(self, block, ty=None, nl=None):
+        """FOR TESTS: the next encode() records the repair stage of its `block`-th encode_block call pass by pass (None: disarm);
+        ty / nl (uint8 arrays, one entry per position of that block): a decision field that replaces the rounds' there."""
+        import numpy as np
+
+        if ty is None and nl is None:
+            rc = self._lib.orz_stream_arm_repair_probe(self._h, -1 if block is None else int(block), None, None, 0)
+        else:
+            ty = np.ascontiguousarray(ty, dtype=np.uint8)
+            nl = np.ascontiguousarray(nl, dtype=np.uint8)
+            if ty.shape != nl.shape or ty.ndim != 1:
+                raise ValueError("ty and nl must be one-dimensional and of the same size")
+            rc = self._lib.orz_stream_arm_repair_probe(self._h, int(block), ty.ctypes.data, nl.ctypes.data, len(ty))
+        _check(rc, "orz_stream_arm_repair_probe")
+
+    def repair_probe(self, name, dtype="u1"):
+        """FOR TESTS: one table of the probed block (orz_stream_repair_probe) as a numpy array; the names are in include/orz_hip.h"""
+        import numpy as np
+
+        size = self._lib.orz_stream_repair_probe(self._h, name.encode(), None, 0)
+        if size < 0:
+            _check(size, "orz_stream_repair_probe")
+        buf = np.empty(size, dtype=np.uint8)
+        self._lib.orz_stream_repair_probe(self._h, name.encode(), buf.ctypes.data, size)
+        return buf.view(dtype)
+
     def close(self):
         if self._h:
             self._lib.orz_stream_free(self._h)

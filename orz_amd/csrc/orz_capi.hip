@@ -209,6 +209,7 @@ struct orz_stream {
     orz::ItemTrace trace;
     bool tracing = false;
     orz::FastTableCapture tables;  // (tests) orz_stream_fast_tables
+    orz::FastRepairProbe probe;    // (tests) orz_stream_repair_probe
     bool fast = false;
     unsigned ftile = orz::kFastTile, frounds = orz::kFastRounds;
     unsigned unit = 0;  // fast mode: bytes per unit of a block; 0 = the encoder's default (a stream that has the GPU to itself)
@@ -237,6 +238,7 @@ struct orz_stream {
         enc = std::move(fresh);
         enc->trace = tracing ? &trace : nullptr;
         enc->tables = &tables;
+        enc->repair_probe = &probe;
     }
     // apply a settings change + rebuild as a transaction: on failure every setting is as before and the old encoder lives on
     template <class Change>
@@ -419,6 +421,10 @@ static orz::StreamEncoder<orz::HipBackend>::DeviceResult stream_encode_device(or
         orz::FastTableCapture& c;
         ~Disarm() { c.arm = -1; }
     } disarm{s->tables};
+    struct DisarmProbe {
+        orz::FastRepairProbe& c;
+        ~DisarmProbe() { c.arm = -1; c.inj_ty.clear(); c.inj_nl.clear(); }
+    } disarm_probe{s->probe};
     struct ClearPatches {  // (tests) an item patch list holds for ONE encode, however it ends
         orz_stream* s;
         ~ClearPatches() { if (s->enc) s->enc->clear_item_patches(); }
@@ -460,6 +466,8 @@ int orz_stream_encode(orz_stream* s, const void* src, size_t n, int src_on_devic
         *dst_len = r.len;
         *dst = p;
         return ORZ_OK;
+    } catch (const std::invalid_argument& e) {  // (tests: a decision field of another size than the armed block's)
+        return fail(ORZ_EINVAL, e.what());
     } catch (const std::bad_alloc&) {
         return fail(ORZ_ENOMEM, "out of host memory");
     } catch (const std::exception& e) {
@@ -539,6 +547,33 @@ long orz_stream_fast_tables(orz_stream* s, int arm_block, const char* name, void
         return 0;
     }
     if (!c.taken) return fail(ORZ_EINVAL, "no block was captured");
+    const std::vector<uint8_t>* t = c.find(name);
+    if (!t) return fail(ORZ_EINVAL, "no such table");
+    if (dst && cap) std::memcpy(dst, t->data(), std::min(cap, t->size()));
+    return (long)t->size();
+}
+
+// (tests) the repair stage of one block of the fast parse, pass by pass, see include/orz_hip.h
+int orz_stream_arm_repair_probe(orz_stream* s, int block, const uint8_t* ty, const uint8_t* nl, size_t n) {
+    if (!s || !s->enc) return fail(ORZ_EINVAL, "null stream");
+    if (!s->enc->fast()) return fail(ORZ_EINVAL, "the exact mode has no repair stage");
+    if (block > 65535) return fail(ORZ_EINVAL, "bad block number");
+    orz::FastRepairProbe& c = s->probe;
+    if (block >= 0 && (ty || nl || n)) {
+        if (const char* why = orz::FastRepairProbe::field_invalid(ty, nl, n)) return fail(ORZ_EINVAL, why);
+    }
+    c.arm = block < 0 ? -1 : block;
+    c.taken = false;
+    c.tab.clear();
+    c.inj_ty.clear();
+    c.inj_nl.clear();
+    if (block >= 0 && n) { c.inj_ty.assign(ty, ty + n); c.inj_nl.assign(nl, nl + n); }
+    return ORZ_OK;
+}
+long orz_stream_repair_probe(orz_stream* s, const char* name, void* dst, size_t cap) {
+    if (!s || !s->enc || !name) return fail(ORZ_EINVAL, "null argument");
+    const orz::FastRepairProbe& c = s->probe;
+    if (!c.taken) return fail(ORZ_EINVAL, "no block was probed");
     const std::vector<uint8_t>* t = c.find(name);
     if (!t) return fail(ORZ_EINVAL, "no such table");
     if (dst && cap) std::memcpy(dst, t->data(), std::min(cap, t->size()));

@@ -51,6 +51,35 @@ struct FastTableCapture {
     }
 };
 
+// (tests) the REPAIR STAGE of one block of the fast parse, pass by pass (StreamEncoder::fast_parse).  Armed like FastTableCapture;
+// the armed block runs outside the captured graph -- the same launches in the same order, with a wait and copies before every
+// FastPassEnd.  Tables: "scalars", "before.{ty,nl,pt,sbits}" (n + 1 positions), per pass k "p<k>.{ty,nl,pt,sbits,src,edge,cok,ctl,
+// mcnt,wcnt}" (ctl as the pass left it, BEFORE FastPassEnd), and "final.{S,TY,ML,W0,ctl}".  `inj_ty` / `inj_nl` (optional): a decision
+// field for every position of the armed block that replaces the rounds' before the first pass (inject_field).
+struct FastRepairProbe {
+    int arm = -1;
+    bool taken = false;
+    std::vector<uint8_t> inj_ty, inj_nl;
+    std::vector<std::pair<std::string, std::vector<uint8_t>>> tab;
+    const std::vector<uint8_t>* find(const char* name) const {
+        for (const auto& t : tab) if (t.first == name) return &t.second;
+        return nullptr;
+    }
+    // the contract of a field (nullptr = kept): ty is literal / WORD / match; nl is 0 (undecided), 1 for a literal, 2 for WORD,
+    // 4..240 for a match; no item reaches beyond the block
+    static const char* field_invalid(const uint8_t* ty, const uint8_t* nl, size_t n) {
+        if (!ty || !nl || !n || n > kNewMax) return "a decision field needs ty and nl for every position of the block";
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t t = ty[i], l = nl[i];
+            if (t != kTyLit && t != kTyWord && t != kTyMatch) return "ty is not literal, WORD or match";
+            const bool ok = l == 0 || (t == kTyLit ? l == 1 : t == kTyWord ? l == 2 : l >= kMinLen && l <= kMaxLen);
+            if (!ok) return "nl does not fit ty";
+            if (i + l > n) return "an item reaches beyond the block";
+        }
+        return nullptr;
+    }
+};
+
 struct EncodeStats {
     uint64_t blocks = 0, sweeps = 0, seg_evals = 0, items = 0, chunks = 0, in_bytes = 0, out_bytes = 0;
     uint64_t rank_redos = 0;  // blocks whose symbol ranking was repeated by the guard (backend symrank)
@@ -887,6 +916,84 @@ class StreamEncoder {
         fclose(f);
     }
 
+    // (tests) the repair stage of the armed block -> *repair_probe (FastRepairProbe).  probe_begin: the optional decision field goes
+    // in behind the last round -- the path's bitmap and the previous-item types follow from it by a walk from the block's first
+    // position (an undecided position on the path becomes the literal it is read as); the first pass's FastFlip over the whole block
+    // brings the slot-order bitmaps into line -- then the state before the first pass.  probe_pass: the state a pass leaves, before
+    // FastPassEnd clears its counters (nothing once the passes are done).  probe_end: the committed arrays.
+    void probe_put(const std::string& name, const void* dev, size_t bytes) {
+        repair_probe->tab.emplace_back(name, std::vector<uint8_t>(bytes));
+        be_.d2h(repair_probe->tab.back().second.data(), dev, bytes);
+    }
+    void probe_state(const std::string& tag, uint32_t n) {
+        probe_put(tag + ".ty", fty_, (size_t)n + 1);
+        probe_put(tag + ".nl", fnl_, (size_t)n + 1);
+        probe_put(tag + ".pt", fpt_, (size_t)n + 1);
+        probe_put(tag + ".sbits", fsbits_, ((size_t)n / 64 + 1) * 8);
+    }
+    // (a block whose parse turns out unstable is parsed again with smaller tiles, fast_parse: the field goes in again and the probe
+    // starts over -- it holds the passes of the parse that is kept.  The lists' rows are filled with 0xa5 first, in the armed block
+    // only: whatever a pass leaves of it beyond a row's entries was not written.)
+    void probe_begin(uint32_t n, uint32_t nsub, uint16_t* mlist, uint16_t* wlist, bool lists) {
+        FastRepairProbe& c = *repair_probe;
+        c.tab.clear();
+        c.taken = false;
+        probe_pass_ = 0;
+        be_.sync();
+        if (!c.inj_ty.empty()) {
+            std::vector<uint8_t> ty(c.inj_ty), nl(c.inj_nl), pt((size_t)n + 1, 0);
+            std::vector<uint64_t> sb((size_t)n / 64 + 8, 0);
+            for (uint32_t x = 0; x < n;) {
+                if (!nl[x]) { ty[x] = kTyLit; nl[x] = 1; }
+                sb[x / 64] |= 1ull << (x & 63);
+                const uint32_t t = ty[x];
+                x += nl[x];
+                pt[x] = (uint8_t)t;
+            }
+            be_.h2d(fty_, ty.data(), n);
+            be_.h2d(fnl_, nl.data(), n);
+            be_.h2d(fpt_, pt.data(), (size_t)n + 1);
+            be_.h2d(fsbits_, sb.data(), sb.size() * 8);
+        }
+        if (lists) {
+            be_.memset(mlist, 0xa5, (size_t)(nsub + 1) * kSubMatches * 2);
+            be_.memset(wlist, 0xa5, (size_t)(nsub + 1) * kSubWords * 2);
+        }
+        const uint64_t sc[8] = {n, fK_, (uint64_t)cfg_.depth, stats.blocks, sizeof(FastCtl), lists ? 1u : 0u, 0, 0};
+        c.tab.emplace_back("scalars", std::vector<uint8_t>((const uint8_t*)sc, (const uint8_t*)sc + sizeof sc));
+        probe_state("before", n);
+    }
+    void probe_pass(uint32_t n, uint32_t nsub, const uint32_t* mcnt, const uint32_t* wcnt, const uint16_t* mlist = nullptr, const uint16_t* wlist = nullptr) {
+        FastCtl h{};
+        be_.d2h(&h, fctl_, sizeof h);
+        if (h.done) return;
+        const std::string tag = "p" + std::to_string(probe_pass_++);
+        probe_state(tag, n);
+        probe_put(tag + ".src", SRC_ + kPre, (size_t)n * 4);
+        probe_put(tag + ".edge", fdirty_, n);
+        probe_put(tag + ".cok", fcok_, 512 * 4);
+        probe_put(tag + ".ctl", fctl_, sizeof(FastCtl));
+        if (mcnt) {  // (the lists form; one row more than the block has subtiles)
+            probe_put(tag + ".mcnt", mcnt, (size_t)nsub * 4);
+            probe_put(tag + ".wcnt", wcnt, (size_t)nsub * 4);
+            probe_put(tag + ".mlist", mlist, (size_t)(nsub + 1) * kSubMatches * 2);
+            probe_put(tag + ".wlist", wlist, (size_t)(nsub + 1) * kSubWords * 2);
+        }
+    }
+    void probe_end(uint32_t n) {
+        probe_put("final.S", S_ + kPre, n);
+        probe_put("final.TY", TY_ + kPre, n);
+        probe_put("final.ML", ML_ + kPre, n);
+        probe_put("final.W0", W0_ + kPre, n);
+        repair_probe->tab.emplace_back("final.ctl", std::vector<uint8_t>((const uint8_t*)&hfin_, (const uint8_t*)&hfin_ + sizeof hfin_));
+        if (pre_items_valid_)  // (lists form: the item count that came with the passes' read-back)
+            repair_probe->tab.emplace_back("final.items", std::vector<uint8_t>((const uint8_t*)pre_two_, (const uint8_t*)pre_two_ + 4));
+        const uint32_t np = (uint32_t)probe_pass_;
+        repair_probe->tab.emplace_back("passes", std::vector<uint8_t>((const uint8_t*)&np, (const uint8_t*)&np + 4));
+        repair_probe->taken = true;
+        repair_probe->arm = -1;
+    }
+
     // (tests) the block's static tables -> *tables, restricted to what the block uses; waits for the prep kernels (a test hook)
     void capture_tables(uint32_t n, uint32_t nent, const uint32_t* slot_keys, const uint32_t* word_keys) {
         FastTableCapture& c = *tables;
@@ -930,6 +1037,11 @@ class StreamEncoder {
     void fast_parse(uint32_t n, uint32_t len, uint32_t nent, const uint32_t* slot_keys, const uint32_t* word_keys, OutT& out) {
         const uint8_t* win = dwin();
         const uint32_t nk = n + 1, K = fK_, nsub = (n + kSub - 1) / kSub, nvw = nent / 64 + 2;  // nvw: words of the item-start bitmap
+        // (tests) this block's repair stage is read out pass by pass: it runs outside the captured graph, the same launches otherwise
+        // (a decision field of another size than the block's is refused here, before the block's first launch)
+        const bool probing = repair_probe && repair_probe->arm >= 0 && (uint64_t)repair_probe->arm == stats.blocks;
+        if (probing && !repair_probe->inj_ty.empty() && (repair_probe->inj_ty.size() != n || repair_probe->inj_nl.size() != n))
+            throw std::invalid_argument("the decision field does not have the armed block's size");
         be_.launch(nk, FastKw{win, kpos_, nk, fkw_});
         be_.launch_waves(((size_t)nk + 63) / 64, FastWordMasks{kpos_, word_keys, krun_, fkw_, wsnap_, nk, fwmask_, fkmeta_}, FastWordMasks::lds_bytes());
         // history item starts per (unified subtile, ctx) and their prefix: what the ring horizons reach back into
@@ -1057,7 +1169,7 @@ class StreamEncoder {
             { const FastHorizon fh{a, 0, std::min(cpt + 1, nsub) - 1}; be_.launch(fh.threads(), fh); }
             // a full block's round loop is the same launch sequence every time: replay it as a hipGraph
             static const bool fused_steps = !(getenv("ORZ_FAST_FUSED") && !strcmp(getenv("ORZ_FAST_FUSED"), "0"));  // (experiments: every kernel a launch of its own)
-            const bool use_graph = be_.graphs_enabled() && (n == kNewMax || n == cur_unit_);
+            const bool use_graph = be_.graphs_enabled() && (n == kNewMax || n == cur_unit_) && !probing;
             const uint64_t gkey = ((uint64_t)R << 58) | ((uint64_t)T << 32) | n;
             const bool replayed = use_graph && be_.graph_replay(gkey);
             struct CaptureGuard {  // a launch that throws inside the capture must not leave the stream capturing
@@ -1168,6 +1280,7 @@ class StreamEncoder {
                     }
                     be_.launch((size_t)nsub * kListThreads, FastWordCheckL{a, pass == 0 ? flaste_ : nullptr, kdirty, wextra, fixlist, fctl_, wlist, wcnt, nsub});
                     be_.launch(kRepairGrid, FastWordApplyL{a, fixlist, rd_out, fcok_, fctl_, kRepairGrid, kdirty});
+                    if (probing) probe_pass(n, nsub, mcnt, wcnt, mlist, wlist);
                     be_.launch(1, FastPassEnd{fctl_});
             };
             // ... and what follows a group of passes in the lists form: the running maximum of the FINAL update bits (FastCommit,
@@ -1186,6 +1299,7 @@ class StreamEncoder {
             // then the control block is read together with the count, ONE wait for both (round 5; before: one after the sixth
             // pass, one for the count).  A block that is not done after kFirstPasses passes (rare) goes on in groups of two with
             // a read-back each, and its commit and count are redone.
+            if (probing) probe_begin(n, nsub, mlist, wlist, repair_lists);
             if (repair_lists && !replayed) {
                 be_.launch(1, FastCtlReset{fctl_});
                 for (int k = 0; k < kFirstPasses; k++, pass++) lists_pass();
@@ -1215,9 +1329,8 @@ class StreamEncoder {
                 }
             } else {
                 be_.launch(1, FastCtlReset{fctl_});
-                for (int group = 0; group < 64 && !h.done; group++) {
-                    const int todo = group == 0 ? 6 : 2;  // (text: five passes that repair something and one that finds nothing)
-                    for (int k = 0; k < todo; k++, pass++) {
+                // (the grid form's pass: the same kernels a thread per position)
+                auto grid_pass = [&]() {
                     be_.launch((size_t)n + 1, FastFlip{a, kPre, len, ~0u, 0, 0, &fctl_->lastflips});
                     // exact ordinals of the item starts: per-(subtile, ctx) counts, their prefix, rank inside the subtile
                     be_.launch_waves(nsub, CountWave{a, 0}, CountWave::lds_bytes());
@@ -1241,8 +1354,12 @@ class StreamEncoder {
                     be_.launch(n, FastWordCheck{a, flaste_, fcut_, fctl_});
                     be_.launch(n, FastWordApply{a, fcut_, rd_out});
 #endif
+                    if (probing) probe_pass(n, nsub, nullptr, nullptr);
                     be_.launch(1, FastPassEnd{fctl_});
-                    }
+                };
+                for (int group = 0; group < 64 && !h.done; group++) {
+                    const int todo = group == 0 ? 6 : 2;  // (text: five passes that repair something and one that finds nothing)
+                    for (int k = 0; k < todo; k++, pass++) grid_pass();
                     be_.d2h(&h, fctl_, sizeof h);
                 }
             }
@@ -1283,6 +1400,7 @@ class StreamEncoder {
         be_.launch(1, FastLtCarry{fpt_, n, fctl_});
         be_.launch(32768, FastWordsCarry{a, flaste_, krunend_, wsnap_});
         be_.launch(256, FastCtxCarry{fcp_, nsub, ctxcount_});
+        if (probing) probe_end(n);
         debug_dump("f", n, &hfin_);
     }
 
@@ -1761,6 +1879,7 @@ class StreamEncoder {
 
     EncodeStats stats;
     ItemTrace* trace = nullptr;  // when set, every block appends its items
+    FastRepairProbe* repair_probe = nullptr;  // (tests) when set and armed, one block's repair stage is copied out pass by pass (fast_parse)
     FastTableCapture* tables = nullptr;  // (tests) when set and armed, one block's static tables are copied out (fast_parse)
 
    private:
@@ -1782,6 +1901,7 @@ class StreamEncoder {
         if (token_held_) { token_held_ = false; be_.parse_token_release(); }
     }
     bool token_held_ = false;
+    int probe_pass_ = 0;             // (tests) passes the armed repair probe has recorded
     bool pre_items_valid_ = false;   // pre_two_ holds the block's item count (and whether its second position starts an item): read
     uint32_t pre_two_[2] = {0, 0};   // with the repairs' control block
     std::vector<void*> owned_;
