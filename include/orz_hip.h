@@ -449,6 +449,39 @@ int orz_reader_set_cache(orz_reader*, uint64_t max_bytes);
 uint64_t orz_reader_cursor_state_bytes(void);
 int orz_reader_cache_stats(orz_reader*, orz_cache_stats* stats);
 
+/* ELEMENT RANGES of plane-encoded tensors (orz_read_elements.h).  A container that orz_members_encode_planes_to_device wrote
+ * holds a tensor of e-byte elements as e members, one per byte plane.  Once the reader knows which members are whose planes it
+ * serves ranges of ELEMENTS, merged on the device: a read decodes only the planes its non-empty ranges touch, each once, and each
+ * only as far as the furthest element asked of its tensor, and a tensor's planes decode side by side.
+ * orz_reader_set_planes: tensor j is the next elems[j] members, plane 0 first; n_tensors == 0 withdraws the declaration.
+ *   ORZ_EINVAL, with nothing changed and nothing launched: an element size other than 1, 2, 4 or 8 (the tensor and the size are
+ *   named); a sum of elems[] different from the member count ("X planes for Y members"); planes of one tensor that decode to
+ *   different sizes (the tensor and the first member that differs are named); elems == NULL with n_tensors > 0.  At most one host
+ *   wait: the member offsets, if the reader has not fetched them yet.  Cursors are kept, and orz_reader_read does afterwards what
+ *   it did before.
+ * orz_reader_tensor_info: the tensors declared (0 = none) and, for the first `cap` of them, the element count and the element
+ *   size; either array may be NULL.
+ * orz_reader_read_elements: range k = count[k] elements of tensor tensor[k] from element first[k]; in any order, overlapping,
+ *   repeated and empty ranges allowed, of one tensor or of several, tensors of single bytes among them.  Their INTERLEAVED bytes
+ *   (count[k] * elems[tensor[k]] each) are written back to back in range order at d_dst (d_cap bytes on the reader's device);
+ *   *dst_len = their sum.  The contract is orz_reader_read's:
+ *   ORZ_EINVAL, before anything reaches the device: no declaration, NULL arrays with n_ranges > 0, a tensor number out of range,
+ *     first + count above the tensor's element count or overflowing (the range is named), lengths whose sum overflows 64 bits,
+ *     a device-resident container that overlaps [d_dst, d_dst + d_cap).
+ *   ORZ_ENOMEM: d_cap below the sum of the bytes.  Nothing is written; *dst_len is filled.
+ *   n_ranges == 0 or all counts zero: ORZ_OK, *dst_len == 0, nothing is launched.
+ *   ORZ_EINVAL naming the member: payload damage in a plane BEFORE the furthest element asked of its tensor (the content of the
+ *     output is then unspecified).  Damage behind that point is not seen.
+ * The output does not depend on what d_dst held and nothing outside [d_dst, d_dst + *dst_len) is written in any case; a failed
+ * read leaves the reader usable.  With a cursor budget planes are hit, resumed, fresh or uncached by orz_reader_read's policy.
+ * The host waits as for orz_reader_read, whatever the number of ranges and tensors: 3 times with the cache off, twice with it
+ * on.  orz_read_stats means what it means there: `ranges` the element ranges, `out_bytes` the sum of the bytes, `gather_ms` the
+ * time of the launch that merges the planes into d_dst. */
+int orz_reader_set_planes(orz_reader*, const uint32_t* elems, size_t n_tensors);
+int orz_reader_tensor_info(orz_reader*, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap);
+int orz_reader_read_elements(orz_reader*, const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges,
+                             uint8_t* d_dst, size_t d_cap, uint64_t* dst_len, orz_read_stats* stats);
+
 /* The Huffman tables of `nchunks` chunks on the device, in the layout the encoder keeps them: a chunk is
  * orz_huffman_stride() = 389 + 389 + 240 entries (symbol ranks after a match / after a literal, long match lengths:
  * /root/reference/src/lz.rs:272-273,298-305), each of the three built as HuffmanTable::new_from_sym_weights(weights, 15)

@@ -259,6 +259,18 @@ SYMBOLS = [
     ("orz_reader_set_cache", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     ("orz_reader_cursor_state_bytes", ctypes.c_uint64, []),
     ("orz_reader_cache_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CacheStats)]),
+    ("orz_reader_set_planes", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
+    (
+        "orz_reader_tensor_info",
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t],
+    ),
+    (
+        "orz_reader_read_elements",
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+         ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ReadStats)],
+    ),
     ("orz_stream_set_item_trace", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("orz_stream_get_item_trace", ctypes.c_long, [ctypes.c_void_p, ctypes.POINTER(Item), ctypes.c_size_t]),
     ("orz_stream_set_item_patches", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),

@@ -695,9 +695,12 @@ class MemberReader:
     `cache_bytes`: a budget of device memory for CURSORS (0 = none, the default): a member's decoded prefix kept with the decoder's
     state at its end, so that a later read decodes only what is not there yet -- walking through a member window by window
     decodes it once, reading a range again or seeking backwards decodes nothing.  A cursor costs the member's decoded size
-    rounded up to 256 plus MemberReader.cursor_state_bytes()."""
+    rounded up to 256 plus MemberReader.cursor_state_bytes().
+    `elems`: the container holds PLANE-ENCODED tensors (MemberEncoder.encode_tensor_planes): the element size of each tensor, as
+    that call returns them (see set_planes).  read_elements / read_tensor then serve ranges of ELEMENTS, their planes merged on the
+    device, and decode each plane only as far as the furthest element asked of its tensor."""
 
-    def __init__(self, src, device=0, members=None, cache_bytes=0):
+    def __init__(self, src, device=0, members=None, cache_bytes=0, elems=None):
         import torch
 
         self._h = None
@@ -730,8 +733,15 @@ class MemberReader:
         _check(self._lib.orz_reader_info(self._h, ctypes.byref(m), ctypes.byref(tot), None, 0), "orz_reader_info")
         self.members, self.total = m.value, tot.value
         self._offsets = None
+        self._tensors = []
         if cache_bytes:
             self.set_cache(cache_bytes)
+        if elems is not None:
+            try:
+                self.set_planes(elems)
+            except Exception:
+                self.close()
+                raise
 
     @staticmethod
     def cursor_state_bytes():
@@ -796,6 +806,86 @@ class MemberReader:
     def read(self, offset, length, out=None, stats=False):
         """`length` decoded bytes from `offset` (read_ranges of one range)"""
         return self.read_ranges([(offset, length)], out=out, stats=stats)
+
+    def set_planes(self, elems):
+        """declare the container as plane-encoded tensors: tensor j is the next elems[j] members, plane 0 first -- the element sizes
+        MemberEncoder.encode_tensor_planes returns.  None or an empty list withdraws the declaration.  Raises OrzError, with nothing
+        changed, for an element size other than 1, 2, 4, 8, planes that are not as many as the members, or planes of one tensor that
+        differ in size.  Cursors are kept and read_ranges does what it did."""
+        if not self._h:
+            raise OrzError("the reader is closed")
+        elems = [] if elems is None else [int(e) for e in elems]
+        if any(e < 0 or e >= 1 << 32 for e in elems):
+            raise ValueError("element sizes are unsigned 32-bit numbers")
+        nt = len(elems)
+        el = (ctypes.c_uint32 * max(nt, 1))(*elems)
+        _check(self._lib.orz_reader_set_planes(self._h, el, nt), "orz_reader_set_planes")
+        n = ctypes.c_uint64()
+        counts = (ctypes.c_uint64 * max(nt, 1))()
+        sizes = (ctypes.c_uint32 * max(nt, 1))()
+        _check(self._lib.orz_reader_tensor_info(self._h, ctypes.byref(n), counts, sizes, nt), "orz_reader_tensor_info")
+        self._tensors = [(counts[j], sizes[j]) for j in range(min(n.value, nt))]
+
+    @property
+    def tensors(self):
+        """[(element count, element size)] of the tensors declared ([] when none are)"""
+        return list(self._tensors)
+
+    def read_elements(self, ranges, out=None, stats=False):
+        """the elements of [(tensor, first, count), ...], their interleaved bytes back to back in that order, as a uint8 tensor on
+        the device (the first bytes of `out` when given: nothing else of it is written)[, stats dict]"""
+        import torch
+
+        if not self._h:
+            raise OrzError("the reader is closed")
+        if out is not None and (out.dtype != torch.uint8 or out.device != self._dev or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous uint8 tensor on %s" % self._dev)
+        ranges = [(int(j), int(f), int(c)) for j, f, c in ranges]
+        if any(v < 0 or v >= 1 << 64 for r in ranges for v in r):
+            raise ValueError("tensor numbers, first elements and counts are unsigned 64-bit numbers")
+        nr = len(ranges)
+        tj = (ctypes.c_uint64 * max(nr, 1))(*[r[0] for r in ranges])
+        tf = (ctypes.c_uint64 * max(nr, 1))(*[r[1] for r in ranges])
+        tc = (ctypes.c_uint64 * max(nr, 1))(*[r[2] for r in ranges])
+        if out is None:
+            # (ranges the library will refuse get a buffer of one byte: the refusal comes from the library, with its message)
+            t = self._tensors
+            ok = all(j < len(t) and f + c <= t[j][0] for j, f, c in ranges)
+            out = torch.empty(sum(c * t[j][1] for j, f, c in ranges) if ok else 0, dtype=torch.uint8, device=self._dev)
+        dst = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self._dev)
+        torch.cuda.current_stream(self._dev).synchronize()
+        dlen = ctypes.c_uint64()
+        st = _native.ReadStats()
+        rc = self._lib.orz_reader_read_elements(self._h, tj, tf, tc, nr, ctypes.c_void_p(dst.data_ptr()), out.numel(), ctypes.byref(dlen),
+                                                ctypes.byref(st))
+        _check(rc, "orz_reader_read_elements")
+        res = out[: dlen.value]
+        return (res, st.as_dict()) if stats else res
+
+    def read_tensor(self, j, first=0, count=None, out=None, dtype=None):
+        """`count` elements of tensor `j` from element `first` (by default all that follow it): read_elements of one range.  With
+        `out`, a contiguous tensor on the device whose element size is the tensor's, the elements are written into it and the
+        written slice is returned; otherwise the bytes, viewed as `dtype` when given."""
+        import torch
+
+        j, first = int(j), int(first)
+        if j < 0 or first < 0 or j >= 1 << 64 or first >= 1 << 64:
+            raise ValueError("the tensor number and the first element are unsigned 64-bit numbers")
+        if count is None:
+            count = max(self._tensors[j][0] - first, 0) if j < len(self._tensors) else 0
+        count = int(count)
+        if count < 0 or count >= 1 << 64:
+            raise ValueError("the count is an unsigned 64-bit number")
+        if out is None:
+            res = self.read_elements([(j, first, count)])
+            return res.view(dtype) if dtype is not None else res
+        if not isinstance(out, torch.Tensor) or out.device != self._dev or not out.is_contiguous():
+            raise ValueError("out must be a contiguous tensor on %s" % self._dev)
+        if j < len(self._tensors) and out.element_size() != self._tensors[j][1]:
+            raise ValueError("out has elements of %d bytes, tensor %d of %d" % (out.element_size(), j, self._tensors[j][1]))
+        flat = out.reshape(-1)
+        got = self.read_elements([(j, first, count)], out=flat.view(torch.uint8))
+        return flat[: got.numel() // out.element_size()]
 
     def close(self):
         if self._h:

@@ -22,6 +22,7 @@
 #include "orz_decode_scatter.h"
 #include "orz_host_decode.h"
 #include "orz_planes.h"
+#include "orz_read_elements.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
 #include "orz_fast_step.h"
@@ -1123,6 +1124,7 @@ int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count,
 struct orz_reader {
     std::unique_ptr<orz::HipBackend> be;
     std::unique_ptr<orz::RangeReader<orz::HipBackend>> rd;  // (declared after the backend: destroyed before it)
+    std::unique_ptr<orz::ElementReader<orz::HipBackend>> el;  // (borrows rd: destroyed before it)
 };
 
 orz_reader* orz_reader_open(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
@@ -1135,6 +1137,7 @@ orz_reader* orz_reader_open(int device, const void* src, size_t n, int src_on_de
         r->be.reset(new orz::HipBackend(device));
         r->rd.reset(new orz::RangeReader<orz::HipBackend>(*r->be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr,
                                                           (const uint64_t*)offs, (const uint64_t*)lens, n_members));
+        r->el.reset(new orz::ElementReader<orz::HipBackend>(*r->rd));
     });
     return rc == ORZ_OK ? r.release() : nullptr;
 }
@@ -1156,6 +1159,15 @@ int orz_reader_info(orz_reader* r, uint64_t* members, uint64_t* total, uint64_t*
     }
 }
 
+namespace {
+void put_read_stats(orz_read_stats* stats, const orz::RangeReadStats& st) {
+    if (!stats) return;
+    stats->ranges = st.ranges; stats->members_decoded = st.members_decoded; stats->decoded_bytes = st.decoded_bytes;
+    stats->out_bytes = st.out_bytes; stats->launches = st.launches; stats->host_waits = st.host_waits;
+    stats->kernel_ms = st.kernel_ms; stats->gather_ms = st.gather_ms; stats->total_s = st.total_s;
+}
+}  // namespace
+
 int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
                     uint64_t* dst_len, orz_read_stats* stats) {
     if (!r || !dst_len) return fail(ORZ_EINVAL, "bad argument");
@@ -1163,11 +1175,33 @@ int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, siz
     uint64_t total = 0;
     const int rc = mapped([&] { r->rd->read(off, len, n_ranges, d_dst, d_cap, total, st, decode_slots()); });
     *dst_len = total;
-    if (stats) {
-        stats->ranges = st.ranges; stats->members_decoded = st.members_decoded; stats->decoded_bytes = st.decoded_bytes;
-        stats->out_bytes = st.out_bytes; stats->launches = st.launches; stats->host_waits = st.host_waits;
-        stats->kernel_ms = st.kernel_ms; stats->gather_ms = st.gather_ms; stats->total_s = st.total_s;
-    }
+    put_read_stats(stats, st);
+    return rc;
+}
+
+int orz_reader_set_planes(orz_reader* r, const uint32_t* elems, size_t n_tensors) {
+    if (!r) return fail(ORZ_EINVAL, "bad argument");
+    return mapped([&] { r->el->set_planes(elems, n_tensors); });
+}
+
+int orz_reader_tensor_info(orz_reader* r, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap) {
+    if (!r) return fail(ORZ_EINVAL, "bad argument");
+    const orz::ElementReader<orz::HipBackend>& el = *r->el;
+    if (n_tensors) *n_tensors = el.elems.size();
+    const size_t k = std::min(cap, el.elems.size());
+    if (counts) std::copy(el.counts.begin(), el.counts.begin() + k, counts);
+    if (elems) std::copy(el.elems.begin(), el.elems.begin() + k, elems);
+    return ORZ_OK;
+}
+
+int orz_reader_read_elements(orz_reader* r, const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges,
+                             uint8_t* d_dst, size_t d_cap, uint64_t* dst_len, orz_read_stats* stats) {
+    if (!r || !dst_len) return fail(ORZ_EINVAL, "bad argument");
+    orz::RangeReadStats st;
+    uint64_t total = 0;
+    const int rc = mapped([&] { r->el->read(tensor, first, count, n_ranges, d_dst, d_cap, total, st, decode_slots()); });
+    *dst_len = total;
+    put_read_stats(stats, st);
     return rc;
 }
 

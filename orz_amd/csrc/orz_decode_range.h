@@ -19,6 +19,9 @@
 // the reader has: upload (ranges and the per-member plan in one copy) -> clear -> DecodeMember launches over the members that
 // fall short -> RangeGather -> [host reads statuses and what was produced]: two host waits.  With the cache off a read is what it
 // was, launch for launch.
+//
+// ELEMENT RANGES of plane-encoded tensors (orz_read_elements.h) are this read with another last launch: RangeReader::run is the
+// part of a read from the upload to the verdicts, and takes the gather that ends it.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -324,21 +327,39 @@ struct RangeReader {
         up[3 * n_ranges] = sum;
         dst_len = sum;
         st.out_bytes = sum;
-        if (d_cap && !d_dst) throw RangeArgumentError("invalid argument: a capacity without a buffer");
-        if (!owned_src && n && d_cap && (const uint8_t*)d_dst < d_src + n && d_src < (const uint8_t*)d_dst + d_cap)
-            throw RangeArgumentError("invalid argument: the container and the output buffer overlap");
-        if (d_cap < sum)
-            throw DecodeCapacityError("output buffer of " + std::to_string(d_cap) + " bytes is too small for " + std::to_string(sum));
+        check_destination(d_dst, d_cap, sum);
         if (sum == 0) {
             st.total_s = be.now() - t0;
             return;
         }
-        const uint64_t M = ix.members;  // (sum > 0: the container has members)
-        if (budget) return read_cached(up, n_ranges, d_dst, sum, st, slots, t0);
+        const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
+        run(up, n_ranges, st, slots, t0, [&](const uint64_t* d_up, const uint64_t* d_place, const uint8_t* base) {
+            be.launch((size_t)RangeGather::units(sum, head), RangeGather{d_up, d_up + 2 * n_ranges, n_ranges, ix.out_off, d_place, ix.out_len, status(),
+                                                                         ix.members, base, d_dst, sum, head});
+        });
+    }
+
+    // what every read refuses of its output buffer, `sum` being the bytes the ranges ask for
+    void check_destination(const uint8_t* d_dst, size_t d_cap, uint64_t sum) const {
+        if (d_cap && !d_dst) throw RangeArgumentError("invalid argument: a capacity without a buffer");
+        if (!owned_src && n && d_cap && d_dst < d_src + n && d_src < d_dst + d_cap)
+            throw RangeArgumentError("invalid argument: the container and the output buffer overlap");
+        if (d_cap < sum)
+            throw DecodeCapacityError("output buffer of " + std::to_string(d_cap) + " bytes is too small for " + std::to_string(sum));
+    }
+
+    // A read from its one upload to the members' verdicts.  `up` = off | len | prefix of n_ranges valid byte ranges that ask for at
+    // least one byte, then whatever else the gather wants uploaded with them.  gather(d_up, d_place, base) queues the launch that
+    // ends the read behind the decode launches: d_up = `up` on the device, a touched member m's bytes lie at base + d_place[m]
+    // (modulo 2^64) as far as the furthest byte asked of it, and status()[m] tells whether they are good.
+    template <class Gather>
+    void run(std::vector<uint64_t>& up, size_t n_ranges, RangeReadStats& st, uint32_t slots, double t0, const Gather& gather) {
+        const uint64_t M = ix.members;  // (bytes are asked for: the container has members)
+        if (budget) return read_cached(up, n_ranges, st, slots, t0, gather);
         grow(d_ranges, ranges_cap, up.size(), false);
         be.h2d(d_ranges, up.data(), up.size() * 8);
         st.host_waits++;
-        const uint64_t *d_off = d_ranges, *d_len = d_ranges + n_ranges, *d_prefix = d_ranges + 2 * n_ranges;
+        const uint64_t *d_off = d_ranges, *d_len = d_ranges + n_ranges;
         be.memset(plan, 0, (size_t)M * 12);  // stop, status (kDecOk = 0), produced
         be.launch(n_ranges, RangePlan{d_off, d_len, n_ranges, ix.out_off, ix.out_len, M, stop()});
         be.launch_waves(1, RangeCompact{stop(), M, list(), arena_off(), rec}, RangeCompact::lds_bytes());
@@ -366,10 +387,8 @@ struct RangeReader {
             a.produced = produced();
             launch_decode<DecodeMember>(be, a, st.launches);
         });
-        const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
         be.timed_begin(1);
-        be.launch((size_t)RangeGather::units(sum, head),
-                  RangeGather{d_off, d_prefix, n_ranges, ix.out_off, arena_off(), ix.out_len, status(), M, arena, d_dst, sum, head});
+        gather(d_ranges, arena_off(), arena);
         be.timed_end(1);
         std::vector<uint32_t> back((size_t)M * 3);
         be.d2h(back.data(), plan, (size_t)M * 12);
@@ -395,7 +414,8 @@ struct RangeReader {
     // does not touch (ties: the lower member; nothing is evicted when even all of them would not make room); otherwise, or when
     // the allocation fails, it is decoded into the transient arena and nothing is kept (UNCACHED).  A member whose decode fails
     // loses its cursor.
-    void read_cached(std::vector<uint64_t>& up, size_t n_ranges, uint8_t* d_dst, uint64_t sum, RangeReadStats& st, uint32_t slots, double t0) {
+    template <class Gather>
+    void read_cached(std::vector<uint64_t>& up, size_t n_ranges, RangeReadStats& st, uint32_t slots, double t0, const Gather& gather) {
         const uint64_t M = ix.members, now = ++reads;
         last = RangeCacheStats{};
         // the plan: RangePlan on the host
@@ -490,7 +510,7 @@ struct RangeReader {
         grow(d_up, up_cap, up.size() * 8, false);
         be.h2d(d_up, up.data(), up.size() * 8);
         st.host_waits++;
-        const uint64_t *d_off = (const uint64_t*)d_up, *d_prefix = d_off + 2 * n_ranges, *d_addr = d_off + r8, *d_cur = d_addr + M;
+        const uint64_t *d_off = (const uint64_t*)d_up, *d_addr = d_off + r8, *d_cur = d_addr + M;
         const uint32_t *d_stop = (const uint32_t*)(d_cur + M), *d_list = d_stop + M;
         be.memset(status(), 0, (size_t)M * 8);  // status (kDecOk = 0), produced
         st.members_decoded = need;
@@ -507,10 +527,8 @@ struct RangeReader {
             a.cursor = d_cur;
             launch_decode<DecodeMemberCursor>(be, a, st.launches);
         });
-        const uint32_t head = (uint32_t)((uintptr_t)d_dst & 15);
         be.timed_begin(1);
-        be.launch((size_t)RangeGather::units(sum, head),
-                  RangeGather{d_off, d_prefix, n_ranges, ix.out_off, d_addr, ix.out_len, status(), M, d_src, d_dst, sum, head});
+        gather(d_off, d_addr, d_src);
         be.timed_end(1);
         std::vector<uint32_t> back((size_t)M * 2);
         be.d2h(back.data(), status(), (size_t)M * 8);

@@ -135,11 +135,9 @@ ORZ_HD void plane_unit_split(const uint8_t* inter, uint8_t* plane, uint64_t pitc
 #pragma unroll
     for (int p = 0; p < E; p++) plane_store16(plane + (uint64_t)p * pitch, pl + 4 * p);
 }
+// the merge's shuffle alone, in registers: 16 bytes of each of E planes (pl) into the 16 E interleaved bytes (w)
 template <int E>
-ORZ_HD void plane_unit_merge(uint8_t* inter, const uint8_t* plane, uint64_t pitch) {
-    uint32_t w[4 * E], pl[4 * E];
-#pragma unroll
-    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, plane + (uint64_t)p * pitch);
+ORZ_HD void plane_merge_shuffle(const uint32_t (&pl)[4 * E], uint32_t (&w)[4 * E]) {
     if constexpr (E == 2) {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -155,6 +153,13 @@ ORZ_HD void plane_unit_merge(uint8_t* inter, const uint8_t* plane, uint64_t pitc
                 plane_transpose4(pl[4 * (4 * h) + k], pl[4 * (4 * h + 1) + k], pl[4 * (4 * h + 2) + k], pl[4 * (4 * h + 3) + k], w[S * (4 * k) + h],
                                  w[S * (4 * k + 1) + h], w[S * (4 * k + 2) + h], w[S * (4 * k + 3) + h]);
     }
+}
+template <int E>
+ORZ_HD void plane_unit_merge(uint8_t* inter, const uint8_t* plane, uint64_t pitch) {
+    uint32_t w[4 * E], pl[4 * E];
+#pragma unroll
+    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, plane + (uint64_t)p * pitch);
+    plane_merge_shuffle<E>(pl, w);
 #pragma unroll
     for (int q = 0; q < E; q++) plane_store16(inter + 16 * q, w + 4 * q);
 }

@@ -1,0 +1,220 @@
+// orz_read_elements.h -- element ranges of PLANE-ENCODED tensors, read through a RangeReader and merged on the device.
+//
+// A container written by orz_members_encode_planes_to_device holds a tensor of e-byte elements as e members, one per byte plane
+// (orz_planes.h).  The reader of byte ranges (orz_decode_range.h) serves bytes of single planes; decode_members_planes takes
+// whole tensors only.  Here the two meet: the caller declares which members are the planes of which tensor (set_planes) and
+// asks for ELEMENTS [first, first + count) of tensors; their interleaved bytes come back to back in range order.
+//
+// The host expands an element range of tensor j into one byte range per plane -- member_off[first_member + p] + first, length
+// count -- and the read is RangeReader's own from there (RangeReader::run: the plan, the arena or the cursors, the decode launches
+// with their stops, the verdicts), so it costs what the bytes asked for cost: a plane is decoded only as far as the furthest
+// element asked of its tensor, once a call, and a tensor's e planes decode side by side.  The expanded byte ranges and the
+// element-range table go up in the read's one upload; the host waits as often as for a byte-range read.
+//
+// What ends the read is ElementGather instead of RangeGather: one launch, one lane per work unit.  A unit of range k is the part
+// of [first, first + count) inside one 16-element block of the PLANE, cut at the plane's multiples of 16 (RangeGather cuts at its
+// destination's).  Arena pieces and cursor buffers start at multiples of 16 and all planes of a tensor share `first`, so the e
+// plane addresses of a unit are co-aligned: an interior unit over planes at multiples of 16 loads e x 16 bytes (plane_load16),
+// interleaves them in registers (plane_merge_shuffle, the shuffles of PlaneMerge) and stores 16 e bytes -- 16 at a time where
+// the unit's destination is a multiple of 16, dwords where it is a multiple of 4.  Head and tail units, units over planes at
+// other addresses and units whose destination is no multiple of 4 go byte by byte; the checks are made at run time.  An element
+// size of 1 is a plain copy through the same kernel.  A unit with a plane whose decode failed writes nothing.  No LDS, no
+// scratch, no atomics; the rule of DESIGN 2a holds: a lane writes its own unit's bytes only and reads what earlier launches wrote.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "orz_decode_range.h"
+#include "orz_planes.h"
+
+namespace orz {
+
+// a dword of device memory at a multiple of 4, stored in the GLOBAL address space (as plane_store16 stores sixteen bytes)
+ORZ_HD void element_store4(uint8_t* d, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(__attribute__((address_space(1))) uint32_t*)d = v;
+#else
+    __builtin_memcpy(d, &v, 4);
+#endif
+}
+
+// One interior unit: 16 bytes of each of the E planes, at multiples of 16 (plane p's at base + place[p] + lo, modulo 2^64), into
+// 16 E interleaved bytes at d, a multiple of 4.
+template <int E>
+ORZ_HD void element_unit_merge(uint8_t* d, uint64_t base, const uint64_t* place, uint64_t lo) {
+    uint32_t w[4 * E], pl[4 * E];
+#pragma unroll
+    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, (const uint8_t*)(uintptr_t)(base + place[p] + lo));
+    if constexpr (E == 1) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) w[q] = pl[q];
+    } else {
+        plane_merge_shuffle<E>(pl, w);
+    }
+    if (((uintptr_t)d & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_store16(d + 16 * q, w + 4 * q);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4 * E; q++) element_store4(d + 4 * q, w[q]);
+    }
+}
+
+// One lane per work unit.  The element ranges as columns (device memory, [n_ranges] each): ufirst = the range's first unit (a
+// prefix sum of the ranges' unit counts; an empty range repeats its successor's, so the search never lands on it), first / count
+// in elements, member = the first member of the range's tensor, dst_off = where the range's bytes go in dst, elem = the element
+// size.  place / status as RangeReader::run hands them to a gather.
+struct ElementGather {
+    const uint64_t *ufirst, *first, *count, *member, *dst_off;
+    const uint32_t* elem;
+    uint64_t n_ranges, units;
+    const uint64_t* place;
+    const uint32_t* status;
+    const uint8_t* base;
+    uint8_t* dst;
+    static uint64_t units_of(uint64_t first, uint64_t count) {
+        return count ? (first + count + (kPlaneUnit - 1)) / kPlaneUnit - first / kPlaneUnit : 0;
+    }
+    ORZ_HD void operator()(size_t unit) const {
+        const uint64_t u = (uint64_t)unit;
+        if (u >= units || !n_ranges) return;
+        const uint64_t k = last_at_or_below(ufirst, n_ranges, u);
+        const uint64_t f = first[k], end = f + count[k];
+        const uint64_t block = (f / kPlaneUnit + (u - ufirst[k])) * kPlaneUnit;
+        const uint64_t lo = block > f ? block : f, hi = block + kPlaneUnit < end ? block + kPlaneUnit : end;
+        if (lo >= hi) return;
+        const uint32_t e = elem[k];
+        const uint64_t* pl = place + member[k];
+        const uint32_t* st = status + member[k];
+        const uint64_t b = (uint64_t)(uintptr_t)base;
+        uint64_t bits = 0;
+        for (uint32_t p = 0; p < e; p++) {
+            if (st[p] != kDecOk) return;
+            bits |= b + pl[p] + lo;
+        }
+        uint8_t* const d = dst + dst_off[k] + (lo - f) * e;
+        if (hi - lo == kPlaneUnit && (bits & 15) == 0 && ((uintptr_t)d & 3) == 0 && (e == 1 || e == 2 || e == 4 || e == 8)) {
+            if (e == 1) element_unit_merge<1>(d, b, pl, lo);
+            else if (e == 2) element_unit_merge<2>(d, b, pl, lo);
+            else if (e == 4) element_unit_merge<4>(d, b, pl, lo);
+            else element_unit_merge<8>(d, b, pl, lo);
+            return;
+        }
+        const uint32_t n = (uint32_t)(hi - lo);
+        for (uint32_t p = 0; p < e; p++) {
+            const uint8_t* s = (const uint8_t*)(uintptr_t)(b + pl[p] + lo);
+            for (uint32_t i = 0; i < n; i++) d[(uint64_t)i * e + p] = s[i];
+        }
+    }
+};
+
+// The declaration of a reader's container as plane-encoded tensors, and the reads of element ranges it allows.  It borrows the
+// reader (declared before it, destroyed after it) and keeps nothing on the device of its own.
+template <class BE>
+struct ElementReader {
+    RangeReader<BE>& rd;
+    std::vector<uint32_t> elems;    // [tensors] element sizes; empty = nothing declared
+    std::vector<uint64_t> first_m;  // [tensors] a tensor's first member
+    std::vector<uint64_t> counts;   // [tensors] its elements = the decoded size of each of its planes
+    explicit ElementReader(RangeReader<BE>& r) : rd(r) {}
+
+    // Tensor j is the next e[j] members, plane 0 first; n_tensors == 0 withdraws the declaration.  Throws RangeArgumentError with
+    // nothing changed.  At most one host wait: the member offsets, if the reader has not fetched them yet.
+    void set_planes(const uint32_t* e, size_t n_tensors) {
+        if (n_tensors && !e) throw RangeArgumentError("invalid argument: tensors without element sizes");
+        std::vector<uint64_t> fm(n_tensors), cnt(n_tensors);
+        uint64_t planes = 0;
+        for (size_t j = 0; j < n_tensors; j++) {
+            if (!plane_elem_ok(e[j]))
+                throw RangeArgumentError("invalid argument: tensor " + std::to_string(j) + " has elements of " + std::to_string(e[j]) +
+                                         " bytes (1, 2, 4 or 8)");
+            fm[j] = planes;
+            planes += e[j];
+        }
+        const uint64_t M = rd.ix.members;
+        if (n_tensors && planes != M)
+            throw RangeArgumentError("invalid argument: " + std::to_string(planes) + " planes for " + std::to_string(M) + " members");
+        if (n_tensors) rd.member_offsets();
+        for (size_t j = 0; j < n_tensors; j++) {
+            const uint64_t f = fm[j];
+            cnt[j] = rd.member_len(f);
+            for (uint64_t m = f + 1; m < f + e[j]; m++)
+                if (rd.member_len(m) != cnt[j])
+                    throw RangeArgumentError("invalid argument: the planes of tensor " + std::to_string(j) + " differ in size: member " +
+                                             std::to_string(m) + " decodes to " + std::to_string(rd.member_len(m)) + " bytes, member " +
+                                             std::to_string(f) + " to " + std::to_string(cnt[j]));
+        }
+        elems.assign(e, e + n_tensors);
+        first_m.swap(fm);
+        counts.swap(cnt);
+    }
+
+    // Elements [first[k], first[k] + count[k]) of tensor tensor[k], their interleaved bytes back to back in range order at d_dst.
+    // dst_len = the sum of the bytes whenever the ranges are valid.  Throws what RangeReader::read throws, for the same reasons.
+    void read(const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
+              uint64_t& dst_len, RangeReadStats& st, uint32_t slots = 2048) {
+        BE& be = rd.be;
+        const double t0 = be.now();
+        st = RangeReadStats{};
+        st.ranges = n_ranges;
+        dst_len = 0;
+        if (elems.empty()) throw RangeArgumentError("invalid argument: the container is not declared as planes of tensors");
+        if (n_ranges && (!tensor || !first || !count)) throw RangeArgumentError("invalid argument: ranges without their arrays");
+        const size_t K = n_ranges, T = elems.size();
+        size_t B = 0;  // byte ranges: one per plane of every element range
+        uint64_t sum = 0;
+        for (size_t k = 0; k < K; k++) {
+            if (tensor[k] >= T)
+                throw RangeArgumentError("invalid argument: range " + std::to_string(k) + " names tensor " + std::to_string(tensor[k]) + " of " +
+                                         std::to_string(T));
+            const uint64_t j = tensor[k];
+            if (first[k] > counts[j] || count[k] > counts[j] - first[k])
+                throw RangeArgumentError("invalid argument: range " + std::to_string(k) + " (tensor " + std::to_string(j) + ", first " +
+                                         std::to_string(first[k]) + ", count " + std::to_string(count[k]) + ") does not lie in the " +
+                                         std::to_string(counts[j]) + " elements");
+            const uint64_t bytes = count[k] * elems[j];  // (a plane has less than 2^32 bytes)
+            if (sum + bytes < sum) throw RangeArgumentError("invalid argument: the ranges' lengths overflow 64 bits");
+            sum += bytes;
+            B += elems[j];
+        }
+        // off | len | prefix of the byte ranges, as RangeReader::run takes them; behind them the element ranges' columns
+        const size_t x = 3 * B + 1;
+        std::vector<uint64_t> up(x + 5 * K + (K + 1) / 2, 0);
+        uint32_t* u_elem = (uint32_t*)(up.data() + x + 5 * K);
+        const std::vector<uint64_t>& m_off = rd.member_offsets();  // (fetched by set_planes: no wait)
+        uint64_t units = 0, at = 0;
+        size_t b = 0;
+        for (size_t k = 0; k < K; k++) {
+            const uint64_t j = tensor[k];
+            const uint32_t e = elems[j];
+            up[x + k] = units;
+            up[x + K + k] = first[k];
+            up[x + 2 * K + k] = count[k];
+            up[x + 3 * K + k] = first_m[j];
+            up[x + 4 * K + k] = at;
+            u_elem[k] = e;
+            units += ElementGather::units_of(first[k], count[k]);
+            for (uint32_t p = 0; p < e; p++, b++) {
+                up[b] = m_off[first_m[j] + p] + first[k];
+                up[B + b] = count[k];
+                up[2 * B + b] = at + (uint64_t)p * count[k];
+            }
+            at += count[k] * e;
+        }
+        up[3 * B] = sum;
+        dst_len = sum;
+        st.out_bytes = sum;
+        rd.check_destination(d_dst, d_cap, sum);
+        if (sum == 0) {
+            st.total_s = be.now() - t0;
+            return;
+        }
+        rd.run(up, B, st, slots, t0, [&](const uint64_t* d_up, const uint64_t* d_place, const uint8_t* base) {
+            const uint64_t* c = d_up + x;
+            be.launch((size_t)units, ElementGather{c, c + K, c + 2 * K, c + 3 * K, c + 4 * K, (const uint32_t*)(c + 5 * K), K, units, d_place,
+                                                   rd.status(), base, d_dst});
+        });
+    }
+};
+
+}  // namespace orz
