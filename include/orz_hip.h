@@ -370,6 +370,40 @@ int orz_decode_members_planes(int device, const void* src, size_t n, int src_on_
                               size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, size_t n_dsts,
                               size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
 uint64_t orz_decode_members_planes_host_waits(void);
+/* PIECES: planes of large tensors cut into members that decode side by side.  A member decodes on one lane, so the number of
+ * members is the decoder's parallelism; with a piece size of P = piece_elems elements (a multiple of 16) plane p of a segment of
+ * `count` elements becomes Q = max(1, ceil(count / P)) consecutive members, piece q holding the plane's bytes
+ * [q P, min(count, (q + 1) P)).  A segment contributes seg_elem x Q members, PLANE-MAJOR: plane 0's pieces 0 .. Q - 1, then plane
+ * 1's.  piece_elems == 0 or >= count: one piece, the layout of orz_members_encode_planes_to_device.  The format does not change:
+ * a piece is an ordinary member, byte for byte what orz_members_encode_segments_to_device writes for the piece's bytes as a
+ * segment of their own.  The caller keeps elems and pieces as it keeps elems today.
+ * orz_members_bound_planes_pieces: a d_cap that always suffices (the sum of the pieces' orz_stream_bound); *n_members_out
+ *   (optional) = the members the encode call writes, sum(seg_elem[k] * Q_k).
+ * orz_members_encode_planes_pieces_to_device: orz_members_encode_planes_to_device -- the same ONE staging buffer and ONE
+ *   PlaneSplit launch -- with one work item per piece.  pieces_out[k] = Q of segment k (n_segs entries); offs / lens have
+ *   sum(seg_elem[k] * Q_k) entries in member order.  With piece_elems == 0 every member is byte for byte that call's.
+ *   ORZ_EINVAL before anything reaches the device: what that call refuses, a piece_elems that is no multiple of 16, a NULL
+ *   pieces_out with n_segs > 0.
+ * orz_decode_members_planes_pieces: orz_decode_members_planes with pieces[j] (n_dsts entries, each >= 1), the pieces per plane
+ *   of destination j, which takes the next elems[j] x pieces[j] members.  Its contract is that call's word for word -- refusals
+ *   before any decode launch, ORZ_ENOMEM naming the first short destination with nothing written, nothing written outside
+ *   [d_dsts[j], d_dsts[j] + out_lens[j]), the same host waits whatever the number of destinations and pieces -- with
+ *   out_lens[j] = elems[j] x ((Q - 1) S + the last piece's size), S being the decoded size of the destination's first member:
+ *   a destination may exceed 4 GiB though every member stays below it.  A plane's pieces decode back to back, straight into a
+ *   destination with elems == 1 and into the plane's place in staging otherwise; the ONE PlaneMerge launch is unchanged.
+ *   ORZ_EINVAL in addition, each naming the destination and the first member that offends: pieces[j] == 0; sum(elems[j] x
+ *   pieces[j]) different from the member count ("X pieces of planes for Y members"); with pieces[j] > 1: S no multiple of 16, a
+ *   piece but the last of another size than S, a last piece of 0 or more than S bytes; planes of one destination whose pieces
+ *   differ in size.
+ * orz_decode_members_planes_pieces_host_waits: the host waits of the calling thread's last such call. */
+size_t orz_members_bound_planes_pieces(const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs, size_t piece_elems, size_t* n_members_out);
+int orz_members_encode_planes_pieces_to_device(orz_members*, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
+                                               size_t n_segs, size_t piece_elems, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs,
+                                               size_t* lens, size_t* pieces_out);
+int orz_decode_members_planes_pieces(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                                     size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems,
+                                     const uint32_t* pieces, size_t n_dsts, size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_members_planes_pieces_host_waits(void);
 /* A measuring hook (tools/dev/planes_bench.py), not a data path: `reps` launches of PlaneSplit (merge == 0) or PlaneMerge over ONE
  * tensor of `count` elements of `elem` bytes (2, 4 or 8) -- interleaved at d_inter, planes at d_planes with a pitch of count
  * rounded up to 16, both on `device` and owned by the caller -- between two events after one warming launch; *ms = milliseconds
@@ -476,8 +510,18 @@ int orz_reader_cache_stats(orz_reader*, orz_cache_stats* stats);
  * read leaves the reader usable.  With a cursor budget planes are hit, resumed, fresh or uncached by orz_reader_read's policy.
  * The host waits as for orz_reader_read, whatever the number of ranges and tensors: 3 times with the cache off, twice with it
  * on.  orz_read_stats means what it means there: `ranges` the element ranges, `out_bytes` the sum of the bytes, `gather_ms` the
- * time of the launch that merges the planes into d_dst. */
+ * time of the launch that merges the planes into d_dst.
+ * orz_reader_set_planes_pieces: orz_reader_set_planes for a container of orz_members_encode_planes_pieces_to_device: tensor j is
+ *   the next elems[j] x pieces[j] members, pieces[j] (>= 1) to a plane, plane-major.  ORZ_EINVAL with nothing changed and nothing
+ *   launched -- an earlier declaration and the cursors stay --: what orz_reader_set_planes refuses, a NULL pieces with
+ *   n_tensors > 0, and what orz_decode_members_planes_pieces refuses of pieces and sizes ("tensor" for "destination").
+ *   orz_reader_tensor_info then reports a tensor's elements over all its pieces, and orz_reader_read_elements serves element
+ *   ranges exactly as above, but decodes ONLY THE PIECES a range touches, each only as far as the furthest element asked inside
+ *   it, all of them side by side: the last rows of a tensor cost its last pieces, not the tensor.  orz_read_stats means what it
+ *   means above, so members_decoded counts pieces; cursors work per member, so pieces are hit, resumed, fresh or uncached as any
+ *   member; the host waits stay 3 and 2. */
 int orz_reader_set_planes(orz_reader*, const uint32_t* elems, size_t n_tensors);
+int orz_reader_set_planes_pieces(orz_reader*, const uint32_t* elems, const uint32_t* pieces, size_t n_tensors);
 int orz_reader_tensor_info(orz_reader*, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap);
 int orz_reader_read_elements(orz_reader*, const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges,
                              uint8_t* d_dst, size_t d_cap, uint64_t* dst_len, orz_read_stats* stats);

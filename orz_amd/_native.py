@@ -205,6 +205,27 @@ SYMBOLS = [
     ),
     ("orz_decode_members_planes_host_waits", ctypes.c_uint64, []),
     (
+        "orz_members_bound_planes_pieces",
+        ctypes.c_size_t,
+        [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)],
+    ),
+    (
+        "orz_members_encode_planes_pieces_to_device",
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+         ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.POINTER(ctypes.c_size_t)],
+    ),
+    (
+        "orz_decode_members_planes_pieces",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.POINTER(DecodeStats)],
+    ),
+    ("orz_decode_members_planes_pieces_host_waits", ctypes.c_uint64, []),
+    (
         "orz_plane_move_time",
         ctypes.c_int,
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
@@ -260,6 +281,7 @@ SYMBOLS = [
     ("orz_reader_cursor_state_bytes", ctypes.c_uint64, []),
     ("orz_reader_cache_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CacheStats)]),
     ("orz_reader_set_planes", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
+    ("orz_reader_set_planes_pieces", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
     (
         "orz_reader_tensor_info",
         ctypes.c_int,

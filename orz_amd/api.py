@@ -476,6 +476,79 @@ class MemberEncoder:
                                                out.data_ptr(), out.numel(), src_on_device=on_dev)
         return (out[: max(o + ln for o, ln in members)] if trim else out), members, elems
 
+    def bound_planes_pieces(self, lengths, elems, piece_elems):
+        """(device bytes that always hold the members, the number of members) of segments of these lengths and element sizes with
+        their planes cut into pieces of `piece_elems` elements (orz_members_bound_planes_pieces)"""
+        n = len(lengths)
+        if len(elems) != n:
+            raise ValueError("one element size per length")
+        arr = (ctypes.c_size_t * max(n, 1))(*[int(x) for x in lengths])
+        el = (ctypes.c_uint32 * max(n, 1))(*[int(e) for e in elems])
+        nm = ctypes.c_size_t()
+        return int(self._lib.orz_members_bound_planes_pieces(arr, el, n, int(piece_elems), ctypes.byref(nm))), nm.value
+
+    def encode_planes_pieces_to_device(self, seg_ptrs, seg_lens, seg_elems, piece_elems, dst_ptr, dst_cap, src_on_device=True):
+        """orz_members_encode_planes_pieces_to_device on raw addresses: encode_planes_to_device with every plane cut into pieces
+        of `piece_elems` elements (a multiple of 16; 0 = never), a member per piece, plane-major.  Returns ([(offset, length)]
+        per member, [pieces per plane of each segment])."""
+        if len(seg_elems) != len(seg_ptrs) or len(seg_lens) != len(seg_ptrs):
+            raise ValueError("one length and one element size per segment")
+        piece_elems = int(piece_elems)
+        if piece_elems < 0 or piece_elems >= 1 << 64:
+            raise ValueError("the piece size is an unsigned 64-bit number")
+        ptrs, lengths, n = self._segment_arrays([int(p) for p in seg_ptrs], [int(x) for x in seg_lens])
+        el = (ctypes.c_uint32 * max(n, 1))(*[int(e) for e in seg_elems])
+        nm = self.bound_planes_pieces([int(x) for x in seg_lens], [int(e) if 0 < int(e) <= 8 else 0 for e in seg_elems], piece_elems)[1]
+        offs, lens = (ctypes.c_size_t * max(nm, 1))(), (ctypes.c_size_t * max(nm, 1))()
+        pieces = (ctypes.c_size_t * max(n, 1))()
+        rc = self._lib.orz_members_encode_planes_pieces_to_device(self._h, ptrs, lengths, el, n, piece_elems, 1 if src_on_device else 0,
+                                                                  ctypes.c_void_p(int(dst_ptr)), int(dst_cap), offs, lens, pieces)
+        _check(rc, "orz_members_encode_planes_pieces_to_device")
+        pieces = [pieces[k] for k in range(n)]
+        return [(offs[k], lens[k]) for k in range(sum(int(e) * q for e, q in zip(seg_elems, pieces)))], pieces
+
+    def encode_tensor_pieces(self, tensors, piece_elems, out=None):
+        """encode_tensor_planes with every plane cut into pieces of `piece_elems` elements (a multiple of 16), a member per piece:
+        tensor k contributes element_size() x Q consecutive members, Q = ceil(numel / piece_elems), plane 0's pieces first.  A
+        member decodes on one lane, so pieces are what lets ONE large tensor decode in parallel and a read of its last rows skip
+        what lies in front of them; each piece restarts the model and costs an encoder pass, so it costs size and encode time.
+        Measured: 2^18 elements a piece is a good default -- a 4 Mi-element bf16 weight decodes in a fourteenth of the
+        time for 0.5 % of size and 1.1 x the encode time (ids: 2 %, 1.7 x); 2^16 where latency matters more (1.6 to 5.7 % of
+        size, 1.8 to 2.9 x the encode time); 2^20 costs nothing and takes a quarter of the time.  piece_elems == 0, or at least a tensor's elements: that tensor's planes stay whole.
+        Returns (container, members, elems, pieces): `pieces` [pieces per plane of each tensor], what decode_planes_into and
+        MemberReader take beside `elems`."""
+        import torch
+
+        if len(self._devices) != 1:
+            raise ValueError("device-resident output needs an encoder on one GPU")
+        dev = torch.device("cuda", self._devices[0])
+        tensors = list(tensors)
+        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
+            raise ValueError("tensors must be contiguous torch tensors")
+        on_dev = bool(tensors) and tensors[0].is_cuda
+        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
+            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
+        elems = [t.element_size() for t in tensors]
+        if any(e > 8 for e in elems):
+            raise ValueError("elements of more than 8 bytes have no byte planes here: view the tensor as a narrower dtype")
+        piece_elems = int(piece_elems)
+        if piece_elems < 0 or piece_elems % 16:
+            raise ValueError("the piece size is a multiple of 16 elements")
+        lengths = [t.numel() * t.element_size() for t in tensors]
+        if out is None:
+            out = torch.empty(self.bound_planes_pieces(lengths, elems, piece_elems)[0], dtype=torch.uint8, device=dev)
+            trim = True
+        else:
+            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
+            trim = False
+        if not tensors:
+            return (out[:0] if trim else out), [], [], []
+        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        members, pieces = self.encode_planes_pieces_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
+                                                              piece_elems, out.data_ptr(), out.numel(), src_on_device=on_dev)
+        return (out[: max(o + ln for o, ln in members)] if trim else out), members, elems, pieces
+
     def close(self):
         if self._h:
             self._lib.orz_members_free(self._h)
@@ -631,12 +704,14 @@ def decode_members_into(src, outs, device=0, members=None, stats=False):
     return res
 
 
-def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False):
+def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None):
     """decode plane members ON THE GPU and merge them (orz_decode_members_planes): `outs[k]` takes the next elems[k] members as
     the byte planes of its elements -- what MemberEncoder.encode_tensor_planes wrote.  `src` and `members` as for
     decode_members_into; `outs`: contiguous tensors on cuda:`device`, each at least as large as its planes together; `elems`:
     the element size of each (1, 2, 4 or 8), by default that of the tensors.  Raises OrzError, with nothing written to any tensor,
     when a size does not fit, the planes are not as many as the members, a tensor's planes differ in size or two tensors overlap.
+    `pieces`: what MemberEncoder.encode_tensor_pieces returned beside `elems` (orz_decode_members_planes_pieces): `outs[k]` takes
+    the next elems[k] x pieces[k] members, pieces[k] to a plane, and all pieces decode side by side.
     Returns [decoded size of each tensor] (and the stats dict, with `host_waits`)."""
     import torch
 
@@ -659,6 +734,10 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     elems = [t.element_size() for t in outs] if elems is None else [int(e) for e in elems]
     if len(elems) != len(outs):
         raise ValueError("one element size per tensor")
+    if pieces is not None:
+        pieces = [int(q) for q in pieces]
+        if len(pieces) != len(outs) or any(q < 0 or q >= 1 << 32 for q in pieces):
+            raise ValueError("one number of pieces per tensor, unsigned 32-bit")
     if members is None:
         offs = lens = None
         nt = 0
@@ -674,14 +753,20 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     nm = ctypes.c_size_t()
     st = _native.DecodeStats()
     torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-    rc = lib.orz_decode_members_planes(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, nd, sizes, ctypes.byref(nm),
-                                       ctypes.byref(st))
-    _check(rc, "orz_decode_members_planes")
+    if pieces is None:
+        rc = lib.orz_decode_members_planes(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, nd, sizes, ctypes.byref(nm),
+                                           ctypes.byref(st))
+        _check(rc, "orz_decode_members_planes")
+    else:
+        pc = (ctypes.c_uint32 * max(nd, 1))(*pieces)
+        rc = lib.orz_decode_members_planes_pieces(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, pc, nd, sizes,
+                                                  ctypes.byref(nm), ctypes.byref(st))
+        _check(rc, "orz_decode_members_planes_pieces")
     del keep
     res = [sizes[k] for k in range(nd)]
     if stats:
         d = st.as_dict()
-        d["host_waits"] = int(lib.orz_decode_members_planes_host_waits())
+        d["host_waits"] = int(lib.orz_decode_members_planes_host_waits() if pieces is None else lib.orz_decode_members_planes_pieces_host_waits())
         return res, d
     return res
 
@@ -698,9 +783,11 @@ class MemberReader:
     rounded up to 256 plus MemberReader.cursor_state_bytes().
     `elems`: the container holds PLANE-ENCODED tensors (MemberEncoder.encode_tensor_planes): the element size of each tensor, as
     that call returns them (see set_planes).  read_elements / read_tensor then serve ranges of ELEMENTS, their planes merged on the
-    device, and decode each plane only as far as the furthest element asked of its tensor."""
+    device, and decode each plane only as far as the furthest element asked of its tensor.
+    `pieces`: beside `elems`, what MemberEncoder.encode_tensor_pieces returned: the tensors' planes are cut into pieces, and a
+    read decodes only the pieces its ranges touch, side by side."""
 
-    def __init__(self, src, device=0, members=None, cache_bytes=0, elems=None):
+    def __init__(self, src, device=0, members=None, cache_bytes=0, elems=None, pieces=None):
         import torch
 
         self._h = None
@@ -738,7 +825,7 @@ class MemberReader:
             self.set_cache(cache_bytes)
         if elems is not None:
             try:
-                self.set_planes(elems)
+                self.set_planes(elems, pieces)
             except Exception:
                 self.close()
                 raise
@@ -807,11 +894,13 @@ class MemberReader:
         """`length` decoded bytes from `offset` (read_ranges of one range)"""
         return self.read_ranges([(offset, length)], out=out, stats=stats)
 
-    def set_planes(self, elems):
+    def set_planes(self, elems, pieces=None):
         """declare the container as plane-encoded tensors: tensor j is the next elems[j] members, plane 0 first -- the element sizes
-        MemberEncoder.encode_tensor_planes returns.  None or an empty list withdraws the declaration.  Raises OrzError, with nothing
-        changed, for an element size other than 1, 2, 4, 8, planes that are not as many as the members, or planes of one tensor that
-        differ in size.  Cursors are kept and read_ranges does what it did."""
+        MemberEncoder.encode_tensor_planes returns.  None or an empty list withdraws the declaration.  With `pieces`, what
+        encode_tensor_pieces returns beside them, tensor j is the next elems[j] x pieces[j] members, pieces[j] to a plane
+        (orz_reader_set_planes_pieces).  Raises OrzError, with nothing changed, for an element size other than 1, 2, 4, 8, planes
+        that are not as many as the members, planes of one tensor that differ in size, or pieces that do not fit together.
+        Cursors are kept and read_ranges does what it did."""
         if not self._h:
             raise OrzError("the reader is closed")
         elems = [] if elems is None else [int(e) for e in elems]
@@ -819,7 +908,14 @@ class MemberReader:
             raise ValueError("element sizes are unsigned 32-bit numbers")
         nt = len(elems)
         el = (ctypes.c_uint32 * max(nt, 1))(*elems)
-        _check(self._lib.orz_reader_set_planes(self._h, el, nt), "orz_reader_set_planes")
+        if pieces is None:
+            _check(self._lib.orz_reader_set_planes(self._h, el, nt), "orz_reader_set_planes")
+        else:
+            pieces = [int(q) for q in pieces]
+            if len(pieces) != nt or any(q < 0 or q >= 1 << 32 for q in pieces):
+                raise ValueError("one number of pieces per tensor, unsigned 32-bit")
+            pc = (ctypes.c_uint32 * max(nt, 1))(*pieces)
+            _check(self._lib.orz_reader_set_planes_pieces(self._h, el, pc, nt), "orz_reader_set_planes_pieces")
         n = ctypes.c_uint64()
         counts = (ctypes.c_uint64 * max(nt, 1))()
         sizes = (ctypes.c_uint32 * max(nt, 1))()

@@ -881,8 +881,13 @@ size_t orz_members_bound_planes(const size_t* seg_len, const uint32_t* seg_elem,
         if (seg_elem[k]) total += (size_t)seg_elem[k] * orz::stream_bound(seg_len[k] / seg_elem[k]);
     return total;
 }
-int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
-                                        size_t n_segs, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens) {
+namespace {
+// pieces to a plane of `count` elements at a piece size of `piece_elems` (0: never cut)
+size_t plane_pieces(size_t count, size_t piece_elems) { return piece_elems && piece_elems < count ? (count + piece_elems - 1) / piece_elems : 1; }
+
+// orz_members_encode_planes_pieces_to_device; pieces_out == nullptr and piece_elems == 0: orz_members_encode_planes_to_device
+int encode_planes_pieces(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs,
+                         size_t piece_elems, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens, size_t* pieces_out) {
     struct Staging {  // the call's one device buffer: the descriptor table, then the planes (and the uploads of host segments)
         void* p = nullptr;
         ~Staging() { if (p) (void)hipFree(p); }
@@ -891,6 +896,8 @@ int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_s
         std::vector<MemberItem> segs;
         if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, segs)) return fail(ORZ_EINVAL, why);
         if (n_segs && !seg_elem) return fail(ORZ_EINVAL, "null element sizes");
+        if (piece_elems % orz::kPlaneUnit)
+            return fail(ORZ_EINVAL, "pieces of " + std::to_string(piece_elems) + " elements are no multiple of " + std::to_string(orz::kPlaneUnit));
         for (size_t k = 0; k < n_segs; k++) {
             if (!orz::plane_elem_ok(seg_elem[k]))
                 return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " has elements of " + std::to_string(seg_elem[k]) + " bytes (1, 2, 4 or 8)");
@@ -907,7 +914,12 @@ int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_s
                     return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
         // the staging buffer's layout: table | per segment, at multiples of 256: [its upload] [its planes]
         size_t n_rows = 0, n_items = 0;
-        for (size_t k = 0; k < n_segs; k++) { n_rows += seg_elem[k] > 1; n_items += seg_elem[k]; }
+        for (size_t k = 0; k < n_segs; k++) {
+            const size_t Q = plane_pieces(segs[k].len / seg_elem[k], piece_elems);
+            n_rows += seg_elem[k] > 1;
+            n_items += seg_elem[k] * Q;
+            if (pieces_out) pieces_out[k] = Q;
+        }
         const auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
         size_t at = up256(orz::plane_table_bytes(n_rows));
         std::vector<size_t> raw_at(n_segs, 0), planes_at(n_segs, 0);
@@ -939,12 +951,17 @@ int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_s
                 be.h2d(stage + raw_at[k], segs[k].p, segs[k].len);
                 d_seg = stage + raw_at[k];
             }
+            // plane p's pieces: its bytes [q P, min(count, (q + 1) P)), an item each (P a multiple of 16: each starts as aligned as the plane)
+            const size_t Q = plane_pieces(count, piece_elems), P = Q > 1 ? piece_elems : count;
+            const auto cut = [&](const uint8_t* plane) {
+                for (size_t q = 0; q < Q; q++) items.push_back(MemberItem{count ? plane + q * P : nullptr, std::min(P, count - q * P)});
+            };
             if (e == 1) {
-                items.push_back(MemberItem{count ? d_seg : nullptr, count});
+                cut(d_seg);
                 continue;
             }
             const size_t pitch = orz::plane_pitch(count);
-            for (uint32_t p = 0; p < e; p++) items.push_back(MemberItem{count ? stage + planes_at[k] + p * pitch : nullptr, count});
+            for (uint32_t p = 0; p < e; p++) cut(stage + planes_at[k] + p * pitch);
             rows.push_back(orz::PlaneRow{(uint64_t)(uintptr_t)d_seg, (uint64_t)(uintptr_t)(stage + planes_at[k]), count, e});
         }
         if (!rows.empty()) {
@@ -963,6 +980,29 @@ int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_s
     } catch (const std::exception& e) {
         return fail(ORZ_ENODEV, e.what());
     }
+}
+}  // namespace
+int orz_members_encode_planes_to_device(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
+                                        size_t n_segs, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens) {
+    return encode_planes_pieces(m, seg_src, seg_len, seg_elem, n_segs, 0, src_on_device, d_dst, d_cap, offs, lens, nullptr);
+}
+size_t orz_members_bound_planes_pieces(const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs, size_t piece_elems, size_t* n_members_out) {
+    size_t total = 0, members = 0;
+    for (size_t k = 0; seg_len && seg_elem && k < n_segs; k++) {
+        if (!seg_elem[k]) continue;
+        const size_t count = seg_len[k] / seg_elem[k], Q = plane_pieces(count, piece_elems);
+        const size_t last = Q > 1 ? count - (Q - 1) * piece_elems : count;
+        total += (size_t)seg_elem[k] * ((Q - 1) * orz::stream_bound(Q > 1 ? piece_elems : 0) + orz::stream_bound(last));
+        members += (size_t)seg_elem[k] * Q;
+    }
+    if (n_members_out) *n_members_out = members;
+    return total;
+}
+int orz_members_encode_planes_pieces_to_device(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem,
+                                               size_t n_segs, size_t piece_elems, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs,
+                                               size_t* lens, size_t* pieces_out) {
+    if (n_segs && !pieces_out) return fail(ORZ_EINVAL, "bad argument");
+    return encode_planes_pieces(m, seg_src, seg_len, seg_elem, n_segs, piece_elems, src_on_device, d_dst, d_cap, offs, lens, pieces_out);
 }
 int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len, size_t* n_members_out) {
     if ((!src && n) || !dst || !dst_len) return fail(ORZ_EINVAL, "bad argument");
@@ -1086,6 +1126,29 @@ int orz_decode_members_planes(int device, const void* src, size_t n, int src_on_
     return rc;
 }
 uint64_t orz_decode_members_planes_host_waits(void) { return g_planes_waits; }
+
+thread_local uint64_t g_pieces_waits = 0;
+int orz_decode_members_planes_pieces(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                                     size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems,
+                                     const uint32_t* pieces, size_t n_dsts, size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats) {
+    g_pieces_waits = 0;
+    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && (!elems || !pieces))) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    uint64_t members = 0;
+    orz::DecodeScatterStats st;
+    static const uint32_t none = 0;  // (no destinations: still "with pieces")
+    const int rc = mapped([&] {
+        orz::HipBackend be(device);
+        orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
+                                   n_members, d_dsts, (const uint64_t*)d_caps, elems, n_dsts, (uint64_t*)out_lens, members, st, decode_slots(),
+                                   pieces ? pieces : &none);
+    });
+    g_pieces_waits = st.host_waits;
+    if (n_members_out) *n_members_out = (size_t)members;
+    if (rc == ORZ_OK) put_stats(stats, st);
+    return rc;
+}
+uint64_t orz_decode_members_planes_pieces_host_waits(void) { return g_pieces_waits; }
 int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {
     if (!d_inter || !d_planes || !count || !ms || reps < 1 || (elem != 2 && elem != 4 && elem != 8)) return fail(ORZ_EINVAL, "bad argument");
     if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
@@ -1182,6 +1245,11 @@ int orz_reader_read(orz_reader* r, const uint64_t* off, const uint64_t* len, siz
 int orz_reader_set_planes(orz_reader* r, const uint32_t* elems, size_t n_tensors) {
     if (!r) return fail(ORZ_EINVAL, "bad argument");
     return mapped([&] { r->el->set_planes(elems, n_tensors); });
+}
+
+int orz_reader_set_planes_pieces(orz_reader* r, const uint32_t* elems, const uint32_t* pieces, size_t n_tensors) {
+    if (!r || (n_tensors && !pieces)) return fail(ORZ_EINVAL, "bad argument");
+    return mapped([&] { r->el->set_planes(elems, n_tensors, pieces); });
 }
 
 int orz_reader_tensor_info(orz_reader* r, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap) {

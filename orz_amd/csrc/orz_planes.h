@@ -20,6 +20,12 @@
 // the capacities and fills the merge's table on the device; PlaneScan (one wavefront) turns the unit counts into the first-unit
 // column and names the first short destination.  The decode launches are DecodeMember's; ONE PlaneMerge launch queued behind
 // them writes the destinations, and the statuses are read once, after it.
+//
+// PIECES.  A member decodes on one lane, so a large tensor's planes may be cut: with a piece size of P elements (a multiple of
+// the work unit) plane p of a tensor is Q = ceil(count / P) consecutive members, bytes [q P, min(count, (q + 1) P)) each, and the
+// tensor's members are plane-major: plane 0's pieces 0 .. Q - 1, then plane 1's.  The format does not change -- a piece is a
+// member -- and neither do split and merge: a plane's pieces lie and decode back to back in the plane's place in staging.  The
+// driver takes pieces[j], the pieces per plane of destination j, beside elems[j]; without them every plane is one piece.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -249,15 +255,47 @@ ORZ_HD uint64_t plane_stage_at(uint64_t off0, uint64_t first_m) { return (off0 +
 // bytes of staging that always suffice for a container of `members` members that decode to `total` bytes
 inline uint64_t plane_stage_bound(uint64_t total, uint64_t members) { return total + 32 * members + 16; }
 
-// One lane per member.  The member's destination j (the last whose first member is at or below m) and plane p; where its bytes
-// go as an offset from `base` modulo 2^64: the destination itself for an element size of 1, else plane p of the destination's
-// place in `stage`; its size for the host's one read.  The lane of a destination's plane 0 judges the capacity against
-// e x the plane's size (the host refuses planes of unequal sizes before it looks at the verdict) and fills the merge's row.
+// What the decoded sizes of the e Q members of one tensor (`what` number j, first member f, plane-major) must satisfy, size_of(m)
+// being member m's: with Q > 1 the pieces of a plane are S bytes each, S = the first one's, a multiple of the work unit, but
+// for the last, which has 1 .. S; and every plane is cut as plane 0 is.  Returns the tensor's elements, (Q - 1) S + the last
+// piece; throws std::runtime_error naming the tensor and the first member that offends.
+template <class SizeOf>
+uint64_t plane_piece_count(const char* what, uint64_t j, uint64_t f, uint32_t e, uint64_t Q, const SizeOf& size_of) {
+    const std::string who = std::string(what) + " " + std::to_string(j);
+    const auto says = [&](uint64_t m) { return "member " + std::to_string(m) + " decodes to " + std::to_string(size_of(m)) + " bytes"; };
+    const uint64_t S = size_of(f), last = size_of(f + Q - 1);
+    if (Q > 1) {
+        if (S % kPlaneUnit)
+            throw std::runtime_error("invalid argument: the pieces of " + who + " are no multiple of " + std::to_string(kPlaneUnit) + " elements: " + says(f));
+        for (uint64_t q = 1; q + 1 < Q; q++)
+            if (size_of(f + q) != S)
+                throw std::runtime_error("invalid argument: the pieces of " + who + " differ in size: " + says(f + q) + ", member " + std::to_string(f) +
+                                         " to " + std::to_string(S));
+        if (last == 0 || last > S)
+            throw std::runtime_error("invalid argument: the last piece of " + who + " has not 1 .. " + std::to_string(S) + " bytes: " + says(f + Q - 1));
+    }
+    for (uint64_t r = Q; r < e * Q; r++)
+        if (size_of(f + r) != size_of(f + r % Q))
+            throw std::runtime_error("invalid argument: the planes of " + who + " differ in size: " + says(f + r) + ", member " + std::to_string(f + r % Q) +
+                                     " to " + std::to_string(size_of(f + r % Q)));
+    return (Q - 1) * S + last;
+}
+
+// One lane per member.  The member's destination j (the last whose first member is at or below m), plane p and piece q -- the
+// destination's members are plane-major, Q = pieces[j] to a plane (pieces == nullptr: one) --; where its bytes go as an offset
+// from `base` modulo 2^64: q S behind the destination itself for an element size of 1, else q S behind plane p of the
+// destination's place in `stage`, S being the size of the destination's first member; its size for the host's one read.  The
+// lane of a destination's first member judges the capacity against e x the plane's size, (Q - 1) S + the last piece in 64 bits
+// (the host refuses pieces and planes of other sizes before it looks at the verdict) and fills the merge's row.
+// plane_stage_at still leaves room when first_m counts pieces: the e Q members of destination j decode to e count bytes, so
+// its successor's place lies at least e count + 32 e Q - 15 bytes behind its own, and e planes of pitch <= count + 15 end
+// e count + 15 e bytes behind it -- 15 e + 15 <= 32 e Q for every Q >= 1; likewise the last one ends inside plane_stage_bound.
 struct PlanePlan {
     const uint64_t* dsts;     // [n_dsts] the destinations' addresses
     const uint64_t* caps;     // [n_dsts] their capacities
-    const uint64_t* first_m;  // [n_dsts] their first members: the prefix sum of elems
+    const uint64_t* first_m;  // [n_dsts] their first members: the prefix sum of elems x pieces
     const uint32_t* elems;    // [n_dsts]
+    const uint32_t* pieces;   // [n_dsts] pieces per plane (each >= 1), or nullptr: one
     uint64_t n_dsts;
     const uint64_t* ix_off;   // [members] the index's prefix sum of out_len
     const uint32_t* out_len;  // [members]
@@ -272,14 +310,15 @@ struct PlanePlan {
     ORZ_HD void operator()(size_t m) const {
         if (m >= members) return;
         const uint64_t j = last_at_or_below(first_m, n_dsts, (uint64_t)m);
-        const uint64_t f = first_m[j], p = (uint64_t)m - f;
+        const uint64_t f = first_m[j], r = (uint64_t)m - f, Q = pieces ? pieces[j] : 1;
+        const uint64_t p = r / Q, q = r % Q;
         const uint32_t e = elems[j], len = out_len[m];
-        const uint64_t count = out_len[f], pitch = plane_pitch(count);
+        const uint64_t S = out_len[f], count = (Q - 1) * S + out_len[f + Q - 1], pitch = plane_pitch(count);
         const uint64_t at = stage + plane_stage_at(ix_off[f], f);
-        out_off[m] = (e == 1 ? dsts[j] : at + p * pitch) - base;
+        out_off[m] = (e == 1 ? dsts[j] : at + p * pitch) + q * S - base;
         sizes[m] = len;
-        if (p) return;
-        verdict[j] = caps[j] < count * e ? kPlShortDestination : (uint32_t)kIxOk;
+        if (r) return;
+        verdict[j] = count > ~(uint64_t)0 / e || caps[j] < count * e ? kPlShortDestination : (uint32_t)kIxOk;
         units[j] = e == 1 ? 0 : plane_units(count);
         t_inter[j] = dsts[j];
         t_plane0[j] = at;
@@ -328,27 +367,31 @@ struct PlaneScan {
 
 // Decodes the members of `src` (n / src_on_device / table / offs / lens / n_table as for decode_members_scatter) into n_dsts
 // destinations in device memory: destination j, d_caps[j] bytes at d_dsts[j], takes the next elems[j] members as the byte planes
-// of elements of elems[j] bytes (1, 2, 4 or 8).  out_lens[j] (when not null) = the destination's size, plane size x elems[j];
-// it is set also when the call fails for a short destination.  d_dsts == nullptr sizes only: nothing is decoded.  Sets `members`.
+// of elements of elems[j] bytes (1, 2, 4 or 8) -- with `pieces`, the next elems[j] x pieces[j] members, pieces[j] to a plane,
+// plane-major.  out_lens[j] (when not null) = the destination's size, plane size x elems[j] (64 bits: a destination of many
+// pieces may exceed 4 GiB though no member does); it is set also when the call fails for a short destination.  d_dsts == nullptr
+// sizes only: nothing is decoded.  Sets `members`.
 // Staging memory, freed before the call returns: at most the container's decoded size and 32 bytes a member
 // (plane_stage_bound); none when every element size is 1.
 // Throws, all before any decode launch and so before a byte of any destination is written:
-//   std::runtime_error      what decode_members_scatter refuses of a container; an element size other than 1, 2, 4, 8; the sum
-//                           of elems different from the member count; planes of one destination of different decoded sizes
-//                           (naming the destination and the first member that differs); a null destination that has bytes; two
+//   std::runtime_error      what decode_members_scatter refuses of a container; an element size other than 1, 2, 4, 8; no pieces
+//                           for a destination; the sum of elems x pieces different from the member count; planes of one
+//                           destination of different decoded sizes, or pieces that plane_piece_count refuses (naming the
+//                           destination and the first member that offends); a null destination that has bytes; two
 //                           destinations that have bytes overlap (whole capacities count); one overlaps a device-resident container
 //   DecodeCapacityError     a capacity below the destination's size, naming the first such destination
 //   std::bad_alloc          no memory for the staging buffer
 // and std::runtime_error naming the member after the launches when a member's payload is damaged: the destinations' content is
 // unspecified then, but nothing outside [d_dsts[j], d_dsts[j] + out_lens[j]) has been written.
-// Host waits (stats.host_waits): decode_members_scatter's for the same container, whatever the number of destinations -- the
-// uploads of a host container and of a table, ONE read of the index record, ONE upload of destinations, capacities, first members
-// and element sizes, ONE read of the plan's record with the sizes, ONE read of the statuses behind the merge: 4, 5 with a table
+// Host waits (stats.host_waits): decode_members_scatter's for the same container, whatever the number of destinations and pieces -- the
+// uploads of a host container and of a table, ONE read of the index record, ONE upload of destinations, capacities, first members,
+// element sizes and pieces, ONE read of the plan's record with the sizes, ONE read of the statuses behind the merge: 4, 5 with a table
 // or a host container, 6 with both.  A sizing call: the index's waits and one read of the sizes.
 template <class BE>
 void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_device, bool table, const uint64_t* offs, const uint64_t* lens,
                            size_t n_table, uint8_t* const* d_dsts, const uint64_t* d_caps, const uint32_t* elems, size_t n_dsts,
-                           uint64_t* out_lens, uint64_t& members, DecodeScatterStats& stats, uint32_t slots = 2048) {
+                           uint64_t* out_lens, uint64_t& members, DecodeScatterStats& stats, uint32_t slots = 2048,
+                           const uint32_t* pieces = nullptr) {
     const double t0 = be.now();
     const bool sizing = d_dsts == nullptr;
     if (n_dsts && !elems) throw std::runtime_error("invalid argument: destinations without element sizes");
@@ -360,7 +403,8 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         if (!plane_elem_ok(elems[j]))
             throw std::runtime_error("invalid argument: destination " + std::to_string(j) + " has elements of " + std::to_string(elems[j]) +
                                      " bytes (1, 2, 4 or 8)");
-        first_m[j + 1] = first_m[j] + elems[j];
+        if (pieces && !pieces[j]) throw std::runtime_error("invalid argument: destination " + std::to_string(j) + " has no pieces");
+        first_m[j + 1] = first_m[j] + (uint64_t)elems[j] * (pieces ? pieces[j] : 1);
         staged = staged || elems[j] > 1;
     }
     DeviceBuffers<BE> own(be);  // the uploaded container, the plan, the staging buffer and the decoder's state
@@ -372,23 +416,19 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     members = M;
     stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
     if (first_m[J] != M)
-        throw std::runtime_error("invalid argument: " + std::to_string(first_m[J]) + " planes for " + std::to_string(M) + " members");
+        throw std::runtime_error("invalid argument: " + std::to_string(first_m[J]) + (pieces ? " pieces of planes for " : " planes for ") +
+                                 std::to_string(M) + " members");
     if (!M) {
         stats.total_s = be.now() - t0;
         return;
     }
-    // planes of one destination of the same size, and the destinations' sizes
+    // planes of one destination of the same size, cut into pieces the same way, and the destinations' sizes
+    std::vector<uint64_t> counts((size_t)J);
     const auto sizes_of = [&](const uint32_t* sizes) {
-        for (uint64_t j = 0; j < J; j++) {
-            const uint64_t f = first_m[j];
-            for (uint64_t m = f + 1; m < first_m[j + 1]; m++)
-                if (sizes[m] != sizes[f])
-                    throw std::runtime_error("invalid argument: the planes of destination " + std::to_string(j) + " differ in size: member " +
-                                             std::to_string(m) + " decodes to " + std::to_string(sizes[m]) + " bytes, member " + std::to_string(f) +
-                                             " to " + std::to_string(sizes[f]));
-        }
+        for (uint64_t j = 0; j < J; j++)
+            counts[j] = plane_piece_count("destination", j, first_m[j], elems[j], pieces ? pieces[j] : 1, [&](uint64_t m) { return (uint64_t)sizes[m]; });
         if (out_lens)
-            for (uint64_t j = 0; j < J; j++) out_lens[j] = (uint64_t)sizes[first_m[j]] * elems[j];
+            for (uint64_t j = 0; j < J; j++) out_lens[j] = counts[j] * elems[j];
     };
     if (sizing) {
         std::vector<uint32_t> back((size_t)M);
@@ -407,10 +447,10 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         }
         if (!stage) throw std::bad_alloc();
     }
-    // the plan's memory, u64 columns first: dsts | caps | first_m | (ONE upload up to here, with elems at its end) out_off[M] |
+    // the plan's memory, u64 columns first: dsts | caps | first_m | (ONE upload up to here, with elems and pieces at its end) out_off[M] |
     // units | table: first, inter, plane0, pitch, count | then u32: elems | table elem | verdict | sizes[M] | the record; sizes
     // and record are read back together
-    const size_t up_words = (size_t)J * 3 + ((size_t)J + 1) / 2;
+    const size_t up_words = (size_t)J * 3 + ((size_t)J * (pieces ? 2 : 1) + 1) / 2;
     std::vector<uint64_t> up(up_words, 0);
     uint64_t base = (uint64_t)(uintptr_t)stage;
     for (uint64_t j = 0; j < J; j++) {
@@ -420,6 +460,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         if (!base) base = up[j];
     }
     std::memcpy(up.data() + 3 * J, elems, (size_t)J * 4);
+    if (pieces) std::memcpy((uint32_t*)(up.data() + 3 * J) + J, pieces, (size_t)J * 4);
     const size_t off_at = up_words * 8, cols_at = off_at + (size_t)M * 8, u32_at = cols_at + (size_t)J * 6 * 8;
     const size_t sizes_at = u32_at + (size_t)J * 8, rec_at = (sizes_at + (size_t)M * 4 + 7) / 8 * 8;
     uint8_t* plan = own.template alloc<uint8_t>(rec_at + sizeof(PlaneRecord), false);
@@ -432,7 +473,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     uint32_t* p_sizes = (uint32_t*)(plan + sizes_at);
     be.h2d(plan, up.data(), up_words * 8);
     stats.host_waits++;
-    be.launch(M, PlanePlan{p_dsts, p_dsts + J, p_dsts + 2 * J, p_elems, J, ix.out_off, ix.out_len, M, base, (uint64_t)(uintptr_t)stage, p_off, p_sizes,
+    be.launch(M, PlanePlan{p_dsts, p_dsts + J, p_dsts + 2 * J, p_elems, pieces ? p_elems + J : nullptr, J, ix.out_off, ix.out_len, M, base, (uint64_t)(uintptr_t)stage, p_off, p_sizes,
                            p_verdict, p_cols, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem});
     be.launch_waves(1, PlaneScan{p_cols, p_verdict, p_cols + J, J, (PlaneRecord*)(plan + rec_at)}, PlaneScan::lds_bytes());
     std::vector<uint8_t> back(rec_at + sizeof(PlaneRecord) - sizes_at);
@@ -445,7 +486,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     // the destinations that have bytes, by address: none null, none inside another, none inside the container
     std::vector<std::pair<uint64_t, uint64_t>> iv;  // (address, destination)
     for (uint64_t j = 0; j < J; j++) {
-        if (!sizes[first_m[j]]) continue;
+        if (!counts[j]) continue;
         if (!d_dsts[j]) throw std::runtime_error("invalid argument: no destination " + std::to_string(j) + " for its planes");
         iv.emplace_back((uint64_t)(uintptr_t)d_dsts[j], j);
     }
@@ -462,7 +503,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     }
     if (rec.status != kIxOk)
         throw DecodeCapacityError("destination " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) + " bytes, too small for " +
-                                  std::to_string((uint64_t)sizes[first_m[rec.bad]] * elems[rec.bad]));
+                                  std::to_string(counts[rec.bad] * elems[rec.bad]));
     decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, p_off, ix.out_len, (uint8_t*)(uintptr_t)base, nullptr, ix.status, 0, 0}, M, slots, own, stats);
     // the merge, queued behind the decode launches on their stream: a plane whose decode failed is merged as whatever staging
     // holds -- bytes of the destination's own size, inside the destination

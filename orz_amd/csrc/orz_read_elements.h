@@ -20,6 +20,13 @@
 // other addresses and units whose destination is no multiple of 4 go byte by byte; the checks are made at run time.  An element
 // size of 1 is a plain copy through the same kernel.  A unit with a plane whose decode failed writes nothing.  No LDS, no
 // scratch, no atomics; the rule of DESIGN 2a holds: a lane writes its own unit's bytes only and reads what earlier launches wrote.
+//
+// PIECES (orz_planes.h): a declaration may say that tensor j's planes are cut into pieces[j] members each, S elements to a piece,
+// S a multiple of 16.  An element range then becomes one byte range per plane PER PIECE IT TOUCHES, so a read decodes only those
+// pieces, each as far as the furthest element asked inside it, side by side -- the last rows of a tensor cost its last pieces.
+// ElementGatherPieces is ElementGather with the columns S and Q: a unit never straddles two pieces, so it finds its piece
+// q = block / S once and takes plane p's bytes from member first + p Q + q at lo - q S.  A declaration without pieces reads
+// through ElementGather exactly as before.
 #pragma once
 #include <string>
 #include <vector>
@@ -38,13 +45,13 @@ ORZ_HD void element_store4(uint8_t* d, uint32_t v) {
 #endif
 }
 
-// One interior unit: 16 bytes of each of the E planes, at multiples of 16 (plane p's at base + place[p] + lo, modulo 2^64), into
+// One interior unit: 16 bytes of each of the E planes, at multiples of 16 (plane p's at base + place[p Q] + lo, modulo 2^64), into
 // 16 E interleaved bytes at d, a multiple of 4.
 template <int E>
-ORZ_HD void element_unit_merge(uint8_t* d, uint64_t base, const uint64_t* place, uint64_t lo) {
+ORZ_HD void element_unit_merge(uint8_t* d, uint64_t base, const uint64_t* place, uint64_t lo, uint64_t Q) {
     uint32_t w[4 * E], pl[4 * E];
 #pragma unroll
-    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, (const uint8_t*)(uintptr_t)(base + place[p] + lo));
+    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, (const uint8_t*)(uintptr_t)(base + place[(uint64_t)p * Q] + lo));
     if constexpr (E == 1) {
 #pragma unroll
         for (int q = 0; q < 4; q++) w[q] = pl[q];
@@ -75,8 +82,10 @@ struct ElementGather {
     static uint64_t units_of(uint64_t first, uint64_t count) {
         return count ? (first + count + (kPlaneUnit - 1)) / kPlaneUnit - first / kPlaneUnit : 0;
     }
-    ORZ_HD void operator()(size_t unit) const {
-        const uint64_t u = (uint64_t)unit;
+    ORZ_HD void operator()(size_t unit) const { gather_unit<false>((uint64_t)unit, nullptr, nullptr); }
+    // unit u; kPieces: the range's tensor has pieces[k] pieces of psize[k] elements to a plane (else one: the columns are not read)
+    template <bool kPieces>
+    ORZ_HD void gather_unit(uint64_t u, const uint64_t* psize, const uint64_t* pieces) const {
         if (u >= units || !n_ranges) return;
         const uint64_t k = last_at_or_below(ufirst, n_ranges, u);
         const uint64_t f = first[k], end = f + count[k];
@@ -84,28 +93,39 @@ struct ElementGather {
         const uint64_t lo = block > f ? block : f, hi = block + kPlaneUnit < end ? block + kPlaneUnit : end;
         if (lo >= hi) return;
         const uint32_t e = elem[k];
-        const uint64_t* pl = place + member[k];
-        const uint32_t* st = status + member[k];
+        // the unit's piece (S is a multiple of the unit: [block, block + 16) lies in one), its planes Q members apart
+        const uint64_t Q = kPieces ? pieces[k] : 1, q = kPieces ? block / psize[k] : 0;
+        const uint64_t in = lo - (kPieces ? q * psize[k] : 0);  // the unit's first byte in its plane's member
+        const uint64_t* pl = place + member[k] + q;
+        const uint32_t* st = status + member[k] + q;
         const uint64_t b = (uint64_t)(uintptr_t)base;
         uint64_t bits = 0;
         for (uint32_t p = 0; p < e; p++) {
-            if (st[p] != kDecOk) return;
-            bits |= b + pl[p] + lo;
+            if (st[(uint64_t)p * Q] != kDecOk) return;
+            bits |= b + pl[(uint64_t)p * Q] + in;
         }
         uint8_t* const d = dst + dst_off[k] + (lo - f) * e;
         if (hi - lo == kPlaneUnit && (bits & 15) == 0 && ((uintptr_t)d & 3) == 0 && (e == 1 || e == 2 || e == 4 || e == 8)) {
-            if (e == 1) element_unit_merge<1>(d, b, pl, lo);
-            else if (e == 2) element_unit_merge<2>(d, b, pl, lo);
-            else if (e == 4) element_unit_merge<4>(d, b, pl, lo);
-            else element_unit_merge<8>(d, b, pl, lo);
+            if (e == 1) element_unit_merge<1>(d, b, pl, in, Q);
+            else if (e == 2) element_unit_merge<2>(d, b, pl, in, Q);
+            else if (e == 4) element_unit_merge<4>(d, b, pl, in, Q);
+            else element_unit_merge<8>(d, b, pl, in, Q);
             return;
         }
         const uint32_t n = (uint32_t)(hi - lo);
         for (uint32_t p = 0; p < e; p++) {
-            const uint8_t* s = (const uint8_t*)(uintptr_t)(b + pl[p] + lo);
+            const uint8_t* s = (const uint8_t*)(uintptr_t)(b + pl[(uint64_t)p * Q] + in);
             for (uint32_t i = 0; i < n; i++) d[(uint64_t)i * e + p] = s[i];
         }
     }
+};
+
+// ElementGather over tensors whose planes are cut into pieces: per range, psize = the elements of a piece (a multiple of 16; of
+// a tensor of one piece any number above its last element's) and pieces = the pieces to a plane.
+struct ElementGatherPieces {
+    ElementGather g;
+    const uint64_t *psize, *pieces;  // [n_ranges]
+    ORZ_HD void operator()(size_t unit) const { g.gather_unit<true>((uint64_t)unit, psize, pieces); }
 };
 
 // The declaration of a reader's container as plane-encoded tensors, and the reads of element ranges it allows.  It borrows the
@@ -115,38 +135,49 @@ struct ElementReader {
     RangeReader<BE>& rd;
     std::vector<uint32_t> elems;    // [tensors] element sizes; empty = nothing declared
     std::vector<uint64_t> first_m;  // [tensors] a tensor's first member
-    std::vector<uint64_t> counts;   // [tensors] its elements = the decoded size of each of its planes
+    std::vector<uint64_t> counts;   // [tensors] its elements = the decoded size of each of its planes, all pieces together
+    std::vector<uint64_t> pieces;   // [tensors] pieces to a plane
+    std::vector<uint64_t> psize;    // [tensors] elements to a piece (of one piece: the tensor's count, or 1 when it has none)
+    bool pieced = false;            // some tensor has more than one piece to a plane
     explicit ElementReader(RangeReader<BE>& r) : rd(r) {}
 
-    // Tensor j is the next e[j] members, plane 0 first; n_tensors == 0 withdraws the declaration.  Throws RangeArgumentError with
-    // nothing changed.  At most one host wait: the member offsets, if the reader has not fetched them yet.
-    void set_planes(const uint32_t* e, size_t n_tensors) {
+    // Tensor j is the next e[j] members, plane 0 first -- with `q`, the next e[j] x q[j] members, q[j] pieces to a plane,
+    // plane-major; n_tensors == 0 withdraws the declaration.  Throws RangeArgumentError with nothing changed.  At most one host
+    // wait: the member offsets, if the reader has not fetched them yet.
+    void set_planes(const uint32_t* e, size_t n_tensors, const uint32_t* q = nullptr) {
         if (n_tensors && !e) throw RangeArgumentError("invalid argument: tensors without element sizes");
-        std::vector<uint64_t> fm(n_tensors), cnt(n_tensors);
+        std::vector<uint64_t> fm(n_tensors), cnt(n_tensors), pcs(n_tensors, 1), psz(n_tensors);
         uint64_t planes = 0;
+        bool cut = false;
         for (size_t j = 0; j < n_tensors; j++) {
             if (!plane_elem_ok(e[j]))
                 throw RangeArgumentError("invalid argument: tensor " + std::to_string(j) + " has elements of " + std::to_string(e[j]) +
                                          " bytes (1, 2, 4 or 8)");
+            if (q && !q[j]) throw RangeArgumentError("invalid argument: tensor " + std::to_string(j) + " has no pieces");
+            if (q) pcs[j] = q[j];
+            cut = cut || pcs[j] > 1;
             fm[j] = planes;
-            planes += e[j];
+            planes += e[j] * pcs[j];
         }
         const uint64_t M = rd.ix.members;
         if (n_tensors && planes != M)
-            throw RangeArgumentError("invalid argument: " + std::to_string(planes) + " planes for " + std::to_string(M) + " members");
+            throw RangeArgumentError("invalid argument: " + std::to_string(planes) + (q ? " pieces of planes for " : " planes for ") +
+                                     std::to_string(M) + " members");
         if (n_tensors) rd.member_offsets();
         for (size_t j = 0; j < n_tensors; j++) {
-            const uint64_t f = fm[j];
-            cnt[j] = rd.member_len(f);
-            for (uint64_t m = f + 1; m < f + e[j]; m++)
-                if (rd.member_len(m) != cnt[j])
-                    throw RangeArgumentError("invalid argument: the planes of tensor " + std::to_string(j) + " differ in size: member " +
-                                             std::to_string(m) + " decodes to " + std::to_string(rd.member_len(m)) + " bytes, member " +
-                                             std::to_string(f) + " to " + std::to_string(cnt[j]));
+            try {
+                cnt[j] = plane_piece_count("tensor", j, fm[j], e[j], pcs[j], [&](uint64_t m) { return (uint64_t)rd.member_len(m); });
+            } catch (const std::runtime_error& err) {
+                throw RangeArgumentError(err.what());
+            }
+            psz[j] = pcs[j] > 1 ? rd.member_len(fm[j]) : cnt[j] ? cnt[j] : 1;
         }
         elems.assign(e, e + n_tensors);
         first_m.swap(fm);
         counts.swap(cnt);
+        pieces.swap(pcs);
+        psize.swap(psz);
+        pieced = cut;
     }
 
     // Elements [first[k], first[k] + count[k]) of tensor tensor[k], their interleaved bytes back to back in range order at d_dst.
@@ -161,7 +192,7 @@ struct ElementReader {
         if (elems.empty()) throw RangeArgumentError("invalid argument: the container is not declared as planes of tensors");
         if (n_ranges && (!tensor || !first || !count)) throw RangeArgumentError("invalid argument: ranges without their arrays");
         const size_t K = n_ranges, T = elems.size();
-        size_t B = 0;  // byte ranges: one per plane of every element range
+        size_t B = 0;  // byte ranges: one per plane, and per piece touched, of every element range
         uint64_t sum = 0;
         for (size_t k = 0; k < K; k++) {
             if (tensor[k] >= T)
@@ -172,17 +203,20 @@ struct ElementReader {
                 throw RangeArgumentError("invalid argument: range " + std::to_string(k) + " (tensor " + std::to_string(j) + ", first " +
                                          std::to_string(first[k]) + ", count " + std::to_string(count[k]) + ") does not lie in the " +
                                          std::to_string(counts[j]) + " elements");
-            const uint64_t bytes = count[k] * elems[j];  // (a plane has less than 2^32 bytes)
+            if (count[k] > ~(uint64_t)0 / elems[j]) throw RangeArgumentError("invalid argument: the ranges' lengths overflow 64 bits");
+            const uint64_t bytes = count[k] * elems[j];
             if (sum + bytes < sum) throw RangeArgumentError("invalid argument: the ranges' lengths overflow 64 bits");
             sum += bytes;
-            B += elems[j];
+            if (!pieced) B += elems[j];
+            else if (count[k]) B += elems[j] * (size_t)((first[k] + count[k] - 1) / psize[j] - first[k] / psize[j] + 1);  // (an empty range: none)
         }
-        // off | len | prefix of the byte ranges, as RangeReader::run takes them; behind them the element ranges' columns
-        const size_t x = 3 * B + 1;
-        std::vector<uint64_t> up(x + 5 * K + (K + 1) / 2, 0);
-        uint32_t* u_elem = (uint32_t*)(up.data() + x + 5 * K);
+        // off | len | prefix of the byte ranges, as RangeReader::run takes them; behind them the element ranges' columns (with
+        // pieces: psize and pieces too)
+        const size_t x = 3 * B + 1, C = pieced ? 7 : 5;
+        std::vector<uint64_t> up(x + C * K + (K + 1) / 2, 0);
+        uint32_t* u_elem = (uint32_t*)(up.data() + x + C * K);
         const std::vector<uint64_t>& m_off = rd.member_offsets();  // (fetched by set_planes: no wait)
-        uint64_t units = 0, at = 0;
+        uint64_t units = 0, at = 0, pre = 0;
         size_t b = 0;
         for (size_t k = 0; k < K; k++) {
             const uint64_t j = tensor[k];
@@ -194,10 +228,25 @@ struct ElementReader {
             up[x + 4 * K + k] = at;
             u_elem[k] = e;
             units += ElementGather::units_of(first[k], count[k]);
-            for (uint32_t p = 0; p < e; p++, b++) {
-                up[b] = m_off[first_m[j] + p] + first[k];
-                up[B + b] = count[k];
-                up[2 * B + b] = at + (uint64_t)p * count[k];
+            if (!pieced) {
+                for (uint32_t p = 0; p < e; p++, b++) {
+                    up[b] = m_off[first_m[j] + p] + first[k];
+                    up[B + b] = count[k];
+                    up[2 * B + b] = at + (uint64_t)p * count[k];
+                }
+            } else {
+                const uint64_t S = psize[j], Q = pieces[j], end = first[k] + count[k];
+                up[x + 5 * K + k] = S;
+                up[x + 6 * K + k] = Q;
+                const uint64_t q0 = first[k] / S, q1 = count[k] ? (end - 1) / S + 1 : q0;
+                for (uint32_t p = 0; p < e; p++)
+                    for (uint64_t q = q0; q < q1; q++, b++) {  // the range's part of piece q of plane p
+                        const uint64_t lo = std::max(first[k], q * S), hi = std::min(end, (q + 1) * S);
+                        up[b] = m_off[first_m[j] + p * Q + q] + (lo - q * S);
+                        up[B + b] = hi - lo;
+                        up[2 * B + b] = pre;
+                        pre += hi - lo;
+                    }
             }
             at += count[k] * e;
         }
@@ -211,8 +260,9 @@ struct ElementReader {
         }
         rd.run(up, B, st, slots, t0, [&](const uint64_t* d_up, const uint64_t* d_place, const uint8_t* base) {
             const uint64_t* c = d_up + x;
-            be.launch((size_t)units, ElementGather{c, c + K, c + 2 * K, c + 3 * K, c + 4 * K, (const uint32_t*)(c + 5 * K), K, units, d_place,
-                                                   rd.status(), base, d_dst});
+            const ElementGather g{c, c + K, c + 2 * K, c + 3 * K, c + 4 * K, (const uint32_t*)(c + C * K), K, units, d_place, rd.status(), base, d_dst};
+            if (pieced) be.launch((size_t)units, ElementGatherPieces{g, c + 5 * K, c + 6 * K});
+            else be.launch((size_t)units, g);
         });
     }
 };
