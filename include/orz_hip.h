@@ -26,6 +26,7 @@ extern "C" {
 #define ORZ_ENOMEM (-12)  /* output buffer too small / allocation failure */
 #define ORZ_EIO (-5)      /* read/write callback failed (io::Error from Read/Write, src/lib.rs:58-63) */
 #define ORZ_ENODEV (-19)  /* no usable HIP device, or a HIP runtime error */
+#define ORZ_EBADMSG (-74) /* decoded bytes whose CRC-32 digest differs from the one given (orz_decode_tensors_verified) */
 
 /* src/lib.rs:31-34,54-55 -- window geometry the object-level API inherits */
 #define ORZ_LZ_BLOCK_SIZE ((1u << 25) - 1)
@@ -404,6 +405,46 @@ int orz_decode_members_planes_pieces(int device, const void* src, size_t n, int 
                                      size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems,
                                      const uint32_t* pieces, size_t n_dsts, size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats);
 uint64_t orz_decode_members_planes_pieces_host_waits(void);
+/* DIGESTS: an end-to-end check of what a decode wrote (orz_crc.h).  The stream format carries no checksum and the device decoder
+ * reports only damage that breaks a stream's structure: a flipped payload bit, a member table whose entries are mixed up or a
+ * piece decoded into the wrong place decode without error to the right number of wrong bytes.  The digest is the zlib CRC-32 of
+ * the tensor's own bytes (reflected polynomial 0xEDB88320, initial value and final xor 0xFFFFFFFF, crc32 of nothing == 0) --
+ * zlib.crc32(t.cpu().numpy().tobytes()) -- whether the tensor is stored whole, as planes or as pieces; the caller keeps it beside
+ * the container as it keeps elems and pieces.
+ * orz_crc32_buffers: crcs[j] = the digest of the lens[j] bytes at bufs[j] (host arrays of n entries).  on_device == 0: the
+ *   buffers lie in host memory and are digested on the host; no device is needed.  Otherwise they lie on `device` and are
+ *   digested there: ONE upload of the table of addresses and lengths, three launches whatever n is (a wavefront per tile of 64
+ *   KiB, a lane per tile, a wavefront per buffer), ONE read of the digests -- 2 host waits for any n.  (The first call of a
+ *   process on a device also uploads the kernels' 17 KiB of tables, once.)  Nothing is written to any buffer and no byte outside
+ *   [bufs[j], bufs[j] + lens[j]) is read, whatever the address.  n == 0: ORZ_OK.  ORZ_EINVAL before anything reaches the
+ *   device: a NULL array with n > 0, a NULL buffer that has bytes.
+ * orz_crc32_combine (host only): the digest of A followed by B from crc_a = that of A, crc_b = that of B and len_b = the length
+ *   of B, which may exceed 4 GiB.
+ * orz_decode_tensors_verified: ONE entry point for the three layouts.  Its contract is orz_decode_members_planes_pieces' word
+ *   for word -- the arguments, the refusals before any decode launch with nothing written, ORZ_ENOMEM naming the first short
+ *   destination, nothing written outside [d_dsts[j], d_dsts[j] + out_lens[j]) -- with these differences.  pieces == NULL: one
+ *   piece each (the layout of orz_decode_members_planes).  elems == NULL: every element size is 1 (the layout of
+ *   orz_decode_members_scatter: a member per destination).  crcs (n_dsts entries) = the digests the destinations must have; it
+ *   is required: NULL is ORZ_EINVAL ("bad argument") before anything reaches the device, except in a sizing call (d_dsts ==
+ *   NULL), which verifies nothing and ignores crcs.  Behind the PlaneMerge launch -- behind the decode launches when nothing is
+ *   merged -- four launches whatever n_dsts is digest the destinations' decoded bytes where they lie: one that makes the table of
+ *   addresses and sizes on the device from what the call's ONE plan upload already holds, and the three of orz_crc32_buffers.  The
+ *   computed digests come back in ONE additional read after the statuses and are compared with crcs on the host: host waits =
+ *   those of orz_decode_members_planes_pieces for the same container, plus 1.  Verdicts, in this order: the refusals before any
+ *   launch, as there; a member whose decode failed, ORZ_EINVAL naming the member; otherwise the first destination whose digest
+ *   differs, ORZ_EBADMSG, orz_last_error() naming the destination, the expected digest and the computed one ("digest mismatch:
+ *   destination J should have CRC-32 0x..., its decoded bytes have 0x...").  The destinations keep what was decoded.  out_crcs
+ *   (optional, n_dsts entries) = the computed digests, filled whenever the digest launches ran: with ORZ_OK, ORZ_EBADMSG and a
+ *   failed member.  ORZ_ENOMEM also when the digests' device memory (4 bytes a destination and a tile) cannot be had, before any
+ *   decode launch.
+ * orz_decode_tensors_verified_host_waits: the host waits of the calling thread's last such call. */
+int orz_crc32_buffers(int device, const void* const* bufs, const size_t* lens, size_t n, int on_device, uint32_t* crcs);
+uint32_t orz_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int orz_decode_tensors_verified(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                                size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems,
+                                const uint32_t* pieces, size_t n_dsts, const uint32_t* crcs, size_t* out_lens, uint32_t* out_crcs,
+                                size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_tensors_verified_host_waits(void);
 /* A measuring hook (tools/dev/planes_bench.py), not a data path: `reps` launches of PlaneSplit (merge == 0) or PlaneMerge over ONE
  * tensor of `count` elements of `elem` bytes (2, 4 or 8) -- interleaved at d_inter, planes at d_planes with a pitch of count
  * rounded up to 16, both on `device` and owned by the caller -- between two events after one warming launch; *ms = milliseconds

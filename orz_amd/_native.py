@@ -226,6 +226,22 @@ SYMBOLS = [
     ),
     ("orz_decode_members_planes_pieces_host_waits", ctypes.c_uint64, []),
     (
+        "orz_crc32_buffers",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_int,
+         ctypes.POINTER(ctypes.c_uint32)],
+    ),
+    ("orz_crc32_combine", ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    (
+        "orz_decode_tensors_verified",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(DecodeStats)],
+    ),
+    ("orz_decode_tensors_verified_host_waits", ctypes.c_uint64, []),
+    (
         "orz_plane_move_time",
         ctypes.c_int,
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,

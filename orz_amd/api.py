@@ -15,9 +15,68 @@ class OrzError(RuntimeError):
     pass
 
 
+class OrzDigestError(OrzError):
+    """decoded bytes whose CRC-32 digest differs from the one given (ORZ_EBADMSG): `.tensor` = the first such tensor, `.expected`
+    and `.computed` = its two digests"""
+
+    def __init__(self, message, tensor, expected, computed):
+        super().__init__(message)
+        self.tensor, self.expected, self.computed = tensor, expected, computed
+
+
+EBADMSG = -74
+
+
 def _check(rc, what):
     if rc != 0:
         raise OrzError("%s failed (%d): %s" % (what, rc, _native.last_error()))
+
+
+def crc32_buffers(tensors, device=0):
+    """[zlib.crc32 of each tensor's bytes] (orz_crc32_buffers): contiguous tensors of any dtype, all on cuda:`device` -- digested
+    there, where they lie, in three launches and two host waits however many they are -- or all on the CPU."""
+    import torch
+
+    lib = _native.load()
+    tensors = list(tensors)
+    if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
+        raise ValueError("tensors must be contiguous torch tensors")
+    on_dev = bool(tensors) and tensors[0].is_cuda
+    dev = torch.device("cuda", int(device))
+    if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
+        raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
+    n = len(tensors)
+    lengths = [t.numel() * t.element_size() for t in tensors]
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[(t.data_ptr() if ln else None) for t, ln in zip(tensors, lengths)])
+    lens = (ctypes.c_size_t * max(n, 1))(*lengths)
+    crcs = (ctypes.c_uint32 * max(n, 1))()
+    if on_dev:
+        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+    _check(lib.orz_crc32_buffers(int(device), ptrs, lens, n, 1 if on_dev else 0, crcs), "orz_crc32_buffers")
+    return [int(crcs[k]) for k in range(n)]
+
+
+def crc32_combine(a, b, len_b):
+    """the digest of A + B from a = that of A, b = that of B and the length of B (orz_crc32_combine; host only)"""
+    a, b, len_b = int(a), int(b), int(len_b)
+    if not (0 <= a < 1 << 32 and 0 <= b < 1 << 32 and 0 <= len_b < 1 << 64):
+        raise ValueError("digests are unsigned 32-bit numbers, the length an unsigned 64-bit one")
+    return int(_native.load().orz_crc32_combine(a, b, len_b))
+
+
+def _digest_array(digests, nd):
+    digests = [int(c) for c in digests]
+    if len(digests) != nd or any(c < 0 or c >= 1 << 32 for c in digests):
+        raise ValueError("one digest per tensor, unsigned 32-bit")
+    return digests, (ctypes.c_uint32 * max(nd, 1))(*digests)
+
+
+def _check_verified(rc, digests, out_crcs):
+    """raises what orz_decode_tensors_verified answered"""
+    if rc == EBADMSG:
+        j = next((k for k, c in enumerate(digests) if out_crcs[k] != c), 0)
+        raise OrzDigestError("orz_decode_tensors_verified failed (%d): %s" % (rc, _native.last_error()), j, digests[j], int(out_crcs[j]))
+    _check(rc, "orz_decode_tensors_verified")
 
 
 def cfg_for_level(level):
@@ -385,11 +444,17 @@ class MemberEncoder:
         _check(rc, "orz_members_encode_segments_to_device")
         return [(offs[k], lens[k]) for k in range(n)]
 
-    def encode_tensors(self, tensors, out=None):
+    def _digests_of(self, tensors, on_dev):
+        """the digests of the INPUT tensors, taken before the encode: they vouch for the source, not for anything the encoder touched"""
+        return crc32_buffers(tensors, device=self._devices[0]) if tensors else []
+
+    def encode_tensors(self, tensors, out=None, digests=False):
         """One member per tensor of `tensors` (contiguous, any dtype, encoded as their bytes; all on this encoder's GPU or all on
         the CPU), left in device memory: returns (container, members).  `container`: a uint8 tensor on the GPU -- `out` when given,
         else one of bound_segments() bytes trimmed to the furthest byte used; `members`: [(offset, length)] per tensor, what
-        MemberReader, decode_members_to_device and decode_members_into take as `members=`."""
+        MemberReader, decode_members_to_device and decode_members_into take as `members=`.  digests=True: the tuple gains a last
+        element, [CRC-32 of each input tensor's bytes] (crc32_buffers on the inputs, before the encode): what
+        decode_members_into takes as `digests=`."""
         import torch
 
         if len(self._devices) != 1:
@@ -410,11 +475,12 @@ class MemberEncoder:
                 raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
             trim = False
         if not tensors:
-            return (out[:0] if trim else out), []
+            return ((out[:0] if trim else out), []) + (([],) if digests else ())
+        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
         torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
         members = self.encode_segments_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths,
                                                  out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return (out[: max(o + ln for o, ln in members)] if trim else out), members
+        return ((out[: max(o + ln for o, ln in members)] if trim else out), members) + crcs
 
     def bound_planes(self, lengths, elems):
         """device bytes that always hold the plane members of segments of these lengths and element sizes
@@ -441,12 +507,13 @@ class MemberEncoder:
         _check(rc, "orz_members_encode_planes_to_device")
         return [(offs[k], lens[k]) for k in range(nm)]
 
-    def encode_tensor_planes(self, tensors, out=None):
+    def encode_tensor_planes(self, tensors, out=None, digests=False):
         """Each tensor of `tensors` as the byte planes of its elements, a member per plane (plane p = byte p of every element):
         tensor k contributes element_size() consecutive members, plane 0 first.  For typed data -- weights shrink by about a
         tenth against encode_tensors, ids and counts severalfold -- and a tensor's planes decode side by side.  Tensors, devices
         and `out` as for encode_tensors; an element size above 8 raises ValueError.  Returns (container, members, elems):
-        `members` [(offset, length)] per plane, `elems` [element size of each tensor]: what decode_planes_into takes."""
+        `members` [(offset, length)] per plane, `elems` [element size of each tensor]: what decode_planes_into takes.
+        digests=True: the tuple gains a last element, [CRC-32 of each input tensor's bytes], as for encode_tensors."""
         import torch
 
         if len(self._devices) != 1:
@@ -470,11 +537,12 @@ class MemberEncoder:
                 raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
             trim = False
         if not tensors:
-            return (out[:0] if trim else out), [], []
+            return ((out[:0] if trim else out), [], []) + (([],) if digests else ())
+        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
         torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
         members = self.encode_planes_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
                                                out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return (out[: max(o + ln for o, ln in members)] if trim else out), members, elems
+        return ((out[: max(o + ln for o, ln in members)] if trim else out), members, elems) + crcs
 
     def bound_planes_pieces(self, lengths, elems, piece_elems):
         """(device bytes that always hold the members, the number of members) of segments of these lengths and element sizes with
@@ -507,7 +575,7 @@ class MemberEncoder:
         pieces = [pieces[k] for k in range(n)]
         return [(offs[k], lens[k]) for k in range(sum(int(e) * q for e, q in zip(seg_elems, pieces)))], pieces
 
-    def encode_tensor_pieces(self, tensors, piece_elems, out=None):
+    def encode_tensor_pieces(self, tensors, piece_elems, out=None, digests=False):
         """encode_tensor_planes with every plane cut into pieces of `piece_elems` elements (a multiple of 16), a member per piece:
         tensor k contributes element_size() x Q consecutive members, Q = ceil(numel / piece_elems), plane 0's pieces first.  A
         member decodes on one lane, so pieces are what lets ONE large tensor decode in parallel and a read of its last rows skip
@@ -516,7 +584,8 @@ class MemberEncoder:
         time for 0.5 % of size and 1.1 x the encode time (ids: 2 %, 1.7 x); 2^16 where latency matters more (1.6 to 5.7 % of
         size, 1.8 to 2.9 x the encode time); 2^20 costs nothing and takes a quarter of the time.  piece_elems == 0, or at least a tensor's elements: that tensor's planes stay whole.
         Returns (container, members, elems, pieces): `pieces` [pieces per plane of each tensor], what decode_planes_into and
-        MemberReader take beside `elems`."""
+        MemberReader take beside `elems`.  digests=True: the tuple gains a last element, [CRC-32 of each input tensor's bytes],
+        as for encode_tensors: a tensor's digest is the same however it is cut."""
         import torch
 
         if len(self._devices) != 1:
@@ -543,11 +612,12 @@ class MemberEncoder:
                 raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
             trim = False
         if not tensors:
-            return (out[:0] if trim else out), [], [], []
+            return ((out[:0] if trim else out), [], [], []) + (([],) if digests else ())
+        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
         torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
         members, pieces = self.encode_planes_pieces_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
                                                               piece_elems, out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return (out[: max(o + ln for o, ln in members)] if trim else out), members, elems, pieces
+        return ((out[: max(o + ln for o, ln in members)] if trim else out), members, elems, pieces) + crcs
 
     def close(self):
         if self._h:
@@ -654,12 +724,14 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
     return tuple(res)
 
 
-def decode_members_into(src, outs, device=0, members=None, stats=False):
+def decode_members_into(src, outs, device=0, members=None, stats=False, digests=None):
     """decode members ON THE GPU, member k into the storage of `outs[k]` (orz_decode_members_scatter): no concatenation is made
     and nothing is copied afterwards.  `src` and `members` as for decode_members_to_device; `outs`: contiguous tensors of any
     dtype on cuda:`device`, one per member, each at least as large as its member (a member of no bytes takes an empty tensor).
     Raises OrzError, with nothing written to any tensor, when a size does not fit, the count differs from the members' or two
-    tensors overlap.  Returns [decoded size of each member] (and the stats dict, with `host_waits`)."""
+    tensors overlap.  `digests`: [CRC-32 of each tensor's bytes] (MemberEncoder.encode_tensors(..., digests=True)): the decoded
+    bytes are digested on the GPU and held to them (orz_decode_tensors_verified, one host wait more); the first tensor that
+    differs raises OrzDigestError.  Returns [decoded size of each member] (and the stats dict, with `host_waits`)."""
     import torch
 
     lib = _native.load()
@@ -691,20 +763,28 @@ def decode_members_into(src, outs, device=0, members=None, stats=False):
     sizes = (ctypes.c_size_t * max(nd, 1))()
     nm = ctypes.c_size_t()
     st = _native.DecodeStats()
+    if digests is not None:
+        digests, want = _digest_array(digests, nd)
     torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-    rc = lib.orz_decode_members_scatter(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, nd, sizes, ctypes.byref(nm),
-                                        ctypes.byref(st))
-    _check(rc, "orz_decode_members_scatter")
+    if digests is None:
+        rc = lib.orz_decode_members_scatter(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, nd, sizes, ctypes.byref(nm),
+                                            ctypes.byref(st))
+        _check(rc, "orz_decode_members_scatter")
+    else:
+        got = (ctypes.c_uint32 * max(nd, 1))()
+        rc = lib.orz_decode_tensors_verified(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, None, None, nd, want, sizes, got,
+                                             ctypes.byref(nm), ctypes.byref(st))
+        _check_verified(rc, digests, got)
     del keep
     res = [sizes[k] for k in range(nd)]
     if stats:
         d = st.as_dict()
-        d["host_waits"] = int(lib.orz_decode_members_scatter_host_waits())
+        d["host_waits"] = int(lib.orz_decode_members_scatter_host_waits() if digests is None else lib.orz_decode_tensors_verified_host_waits())
         return res, d
     return res
 
 
-def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None):
+def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None, digests=None):
     """decode plane members ON THE GPU and merge them (orz_decode_members_planes): `outs[k]` takes the next elems[k] members as
     the byte planes of its elements -- what MemberEncoder.encode_tensor_planes wrote.  `src` and `members` as for
     decode_members_into; `outs`: contiguous tensors on cuda:`device`, each at least as large as its planes together; `elems`:
@@ -712,6 +792,10 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     when a size does not fit, the planes are not as many as the members, a tensor's planes differ in size or two tensors overlap.
     `pieces`: what MemberEncoder.encode_tensor_pieces returned beside `elems` (orz_decode_members_planes_pieces): `outs[k]` takes
     the next elems[k] x pieces[k] members, pieces[k] to a plane, and all pieces decode side by side.
+    `digests`: [CRC-32 of each tensor's bytes] (what the encode calls return with digests=True): the merged bytes are digested on
+    the GPU and held to them (orz_decode_tensors_verified, with or without `pieces`; one host wait more) -- a flipped payload bit,
+    a member table whose entries are mixed up and a piece in the wrong place all decode without an error otherwise; the first
+    tensor that differs raises OrzDigestError (.tensor, .expected, .computed), the tensors keeping what was decoded.
     Returns [decoded size of each tensor] (and the stats dict, with `host_waits`)."""
     import torch
 
@@ -752,8 +836,16 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     sizes = (ctypes.c_size_t * max(nd, 1))()
     nm = ctypes.c_size_t()
     st = _native.DecodeStats()
+    if digests is not None:
+        digests, want = _digest_array(digests, nd)
     torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-    if pieces is None:
+    if digests is not None:
+        pc = None if pieces is None else (ctypes.c_uint32 * max(nd, 1))(*pieces)
+        got = (ctypes.c_uint32 * max(nd, 1))()
+        rc = lib.orz_decode_tensors_verified(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, pc, nd, want, sizes, got,
+                                             ctypes.byref(nm), ctypes.byref(st))
+        _check_verified(rc, digests, got)
+    elif pieces is None:
         rc = lib.orz_decode_members_planes(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, nd, sizes, ctypes.byref(nm),
                                            ctypes.byref(st))
         _check(rc, "orz_decode_members_planes")
@@ -766,7 +858,8 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     res = [sizes[k] for k in range(nd)]
     if stats:
         d = st.as_dict()
-        d["host_waits"] = int(lib.orz_decode_members_planes_host_waits() if pieces is None else lib.orz_decode_members_planes_pieces_host_waits())
+        d["host_waits"] = int(lib.orz_decode_tensors_verified_host_waits() if digests is not None else
+                              lib.orz_decode_members_planes_host_waits() if pieces is None else lib.orz_decode_members_planes_pieces_host_waits())
         return res, d
     return res
 
@@ -929,7 +1022,8 @@ class MemberReader:
 
     def read_elements(self, ranges, out=None, stats=False):
         """the elements of [(tensor, first, count), ...], their interleaved bytes back to back in that order, as a uint8 tensor on
-        the device (the first bytes of `out` when given: nothing else of it is written)[, stats dict]"""
+        the device (the first bytes of `out` when given: nothing else of it is written)[, stats dict].  Unverified: a part of a
+        tensor has no digest -- read_tensor(j, digest=...) checks a whole one."""
         import torch
 
         if not self._h:
@@ -958,10 +1052,19 @@ class MemberReader:
         res = out[: dlen.value]
         return (res, st.as_dict()) if stats else res
 
-    def read_tensor(self, j, first=0, count=None, out=None, dtype=None):
+    def _hold_to(self, j, digest, got):
+        """raises OrzDigestError unless the bytes of `got` (tensor j, whole) have the digest"""
+        computed = crc32_buffers([got], device=self._dev.index)[0]
+        if computed != digest:
+            raise OrzDigestError("digest mismatch: tensor %d should have CRC-32 0x%08x, its decoded bytes have 0x%08x" % (j, digest, computed),
+                                 j, digest, computed)
+
+    def read_tensor(self, j, first=0, count=None, out=None, dtype=None, digest=None):
         """`count` elements of tensor `j` from element `first` (by default all that follow it): read_elements of one range.  With
         `out`, a contiguous tensor on the device whose element size is the tensor's, the elements are written into it and the
-        written slice is returned; otherwise the bytes, viewed as `dtype` when given."""
+        written slice is returned; otherwise the bytes, viewed as `dtype` when given.  `digest`: the CRC-32 of the WHOLE tensor's
+        bytes -- only with first == 0 and count None or all of it, else ValueError: after the read the result is digested on the
+        GPU (crc32_buffers) and OrzDigestError raised when it differs."""
         import torch
 
         j, first = int(j), int(first)
@@ -972,8 +1075,16 @@ class MemberReader:
         count = int(count)
         if count < 0 or count >= 1 << 64:
             raise ValueError("the count is an unsigned 64-bit number")
+        if digest is not None:
+            digest = int(digest)
+            if digest < 0 or digest >= 1 << 32:
+                raise ValueError("a digest is an unsigned 32-bit number")
+            if first != 0 or (j < len(self._tensors) and count != self._tensors[j][0]):
+                raise ValueError("a digest vouches for a whole tensor: a partial read has none")
         if out is None:
             res = self.read_elements([(j, first, count)])
+            if digest is not None:
+                self._hold_to(j, digest, res)
             return res.view(dtype) if dtype is not None else res
         if not isinstance(out, torch.Tensor) or out.device != self._dev or not out.is_contiguous():
             raise ValueError("out must be a contiguous tensor on %s" % self._dev)
@@ -981,6 +1092,8 @@ class MemberReader:
             raise ValueError("out has elements of %d bytes, tensor %d of %d" % (out.element_size(), j, self._tensors[j][1]))
         flat = out.reshape(-1)
         got = self.read_elements([(j, first, count)], out=flat.view(torch.uint8))
+        if digest is not None:
+            self._hold_to(j, digest, got)
         return flat[: got.numel() // out.element_size()]
 
     def close(self):

@@ -68,13 +68,15 @@ void put_stats(orz_decode_stats* out, const orz::DecodeStats& st) {
     out->members = st.members; out->in_bytes = st.in_bytes; out->out_bytes = st.out_bytes;
     out->launches = st.launches; out->kernel_ms = st.kernel_ms; out->total_s = st.total_s;
 }
-// Runs f.  What it throws becomes the thread's message and ORZ_ENOMEM (a buffer of the caller's that is too small, memory that
-// ran out) or ORZ_EINVAL (anything else).
+// Runs f.  What it throws becomes the thread's message and ORZ_EBADMSG (a digest that differs), ORZ_ENOMEM (a buffer of the
+// caller's that is too small, memory that ran out) or ORZ_EINVAL (anything else).
 template <class F>
 int mapped(F&& f) {
     try {
         f();
         return ORZ_OK;
+    } catch (const orz::DecodeDigestError& e) {
+        return fail(ORZ_EBADMSG, e.what());
     } catch (const orz::DecodeCapacityError& e) {
         return fail(ORZ_ENOMEM, e.what());
     } catch (const std::bad_alloc& e) {
@@ -1149,6 +1151,71 @@ int orz_decode_members_planes_pieces(int device, const void* src, size_t n, int 
     return rc;
 }
 uint64_t orz_decode_members_planes_pieces_host_waits(void) { return g_pieces_waits; }
+
+// ------------------------------------------------------------------------------ CRC-32 digests (orz_crc.h)
+// The kernels' tables on `device`: computed and uploaded once per device and process, never freed.  (A copy of its own, not one of
+// a backend's stream: it is no host wait of the call that happens to be the first.)
+static const uint32_t* crc_device_image(int device) {
+    static std::mutex m;
+    static std::map<int, uint32_t*> images;
+    std::lock_guard<std::mutex> lk(m);
+    auto it = images.find(device);
+    if (it != images.end()) return it->second;
+    ORZ_HIP_CHECK(hipSetDevice(device));
+    uint32_t* d = nullptr;
+    ORZ_HIP_CHECK(hipMalloc((void**)&d, orz::kCrcImageWords * 4));
+    const hipError_t e = hipMemcpy(d, orz::crc_host_image(), orz::kCrcImageWords * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e) + " at the upload of the CRC tables");
+    }
+    images[device] = d;
+    return d;
+}
+
+int orz_crc32_buffers(int device, const void* const* bufs, const size_t* lens, size_t n, int on_device, uint32_t* crcs) {
+    if (!n) return ORZ_OK;
+    if (!bufs || !lens || !crcs) return fail(ORZ_EINVAL, "bad argument");
+    for (size_t j = 0; j < n; j++)
+        if (!bufs[j] && lens[j]) return fail(ORZ_EINVAL, "buffer " + std::to_string(j) + " is NULL and has bytes");
+    if (!on_device) {
+        for (size_t j = 0; j < n; j++) crcs[j] = orz::crc32_host((const uint8_t*)bufs[j], lens[j]);
+        return ORZ_OK;
+    }
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    return mapped([&] {
+        orz::HipBackend be(device);
+        std::vector<uint64_t> addrs(n);
+        for (size_t j = 0; j < n; j++) addrs[j] = (uint64_t)(uintptr_t)bufs[j];
+        uint64_t waits = 0;
+        orz::crc32_device_buffers(be, crc_device_image(device), addrs.data(), (const uint64_t*)lens, n, crcs, waits);
+    });
+}
+uint32_t orz_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return orz::crc32_combine(crc_a, crc_b, len_b); }
+
+thread_local uint64_t g_verified_waits = 0;
+int orz_decode_tensors_verified(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens, size_t n_members,
+                                uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, const uint32_t* pieces, size_t n_dsts,
+                                const uint32_t* crcs, size_t* out_lens, uint32_t* out_crcs, size_t* n_members_out, orz_decode_stats* stats) {
+    g_verified_waits = 0;
+    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && (!d_caps || !crcs))) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    uint64_t members = 0;
+    orz::DecodeScatterStats st;
+    const int rc = mapped([&] {
+        const std::vector<uint32_t> ones(elems ? 0 : n_dsts + 1, 1);  // (no element sizes: bytes, the scatter layout)
+        orz::HipBackend be(device);
+        const orz::CrcCheck check{d_dsts ? crc_device_image(device) : nullptr, crcs, out_crcs};
+        orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
+                                   n_members, d_dsts, (const uint64_t*)d_caps, elems ? elems : ones.data(), n_dsts, (uint64_t*)out_lens, members, st,
+                                   decode_slots(), pieces, &check);
+    });
+    g_verified_waits = st.host_waits;
+    if (n_members_out) *n_members_out = (size_t)members;
+    if (rc == ORZ_OK) put_stats(stats, st);
+    return rc;
+}
+uint64_t orz_decode_tensors_verified_host_waits(void) { return g_verified_waits; }
 int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {
     if (!d_inter || !d_planes || !count || !ms || reps < 1 || (elem != 2 && elem != 4 && elem != 8)) return fail(ORZ_EINVAL, "bad argument");
     if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");

@@ -39,6 +39,7 @@
 #include "orz_decode_drive.h"
 #include "orz_decode_range.h"    // (last_at_or_below)
 #include "orz_decode_scatter.h"  // (DecodeScatterStats)
+#include "orz_crc.h"             // (the digests of a verified decode)
 
 namespace orz {
 
@@ -387,14 +388,23 @@ struct PlaneScan {
 // uploads of a host container and of a table, ONE read of the index record, ONE upload of destinations, capacities, first members,
 // element sizes and pieces, ONE read of the plan's record with the sizes, ONE read of the statuses behind the merge: 4, 5 with a table
 // or a host container, 6 with both.  A sizing call: the index's waits and one read of the sizes.
+// VERIFIED (`check` not null; null for every other caller, for whom nothing here changes): the destinations' decoded bytes are
+// held to the CRC-32 digests check->expect[j] (orz_crc.h).  Behind the merge -- behind the decode launches when nothing is merged
+// -- ONE CrcPlan launch makes the digest table on the device from what the plan's upload holds, and CrcTiles, CrcFold and CrcSum run
+// over the destinations: 4 launches more, whatever the number of destinations.  The digests come back in ONE additional read
+// after the statuses (host waits: the above plus 1) and are compared here.  A member whose decode failed is reported first, as
+// above; otherwise the first destination whose digest differs throws DecodeDigestError.  check->computed (when not null) is
+// filled whenever the digest launches ran.  A sizing call verifies nothing; no digests for destinations is refused before any
+// launch, and so is memory for the digests that cannot be had (std::bad_alloc).
 template <class BE>
 void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_device, bool table, const uint64_t* offs, const uint64_t* lens,
                            size_t n_table, uint8_t* const* d_dsts, const uint64_t* d_caps, const uint32_t* elems, size_t n_dsts,
                            uint64_t* out_lens, uint64_t& members, DecodeScatterStats& stats, uint32_t slots = 2048,
-                           const uint32_t* pieces = nullptr) {
+                           const uint32_t* pieces = nullptr, const CrcCheck* check = nullptr) {
     const double t0 = be.now();
     const bool sizing = d_dsts == nullptr;
     if (n_dsts && !elems) throw std::runtime_error("invalid argument: destinations without element sizes");
+    if (check && !sizing && n_dsts && (!check->expect || !check->d_image)) throw std::runtime_error("invalid argument: destinations without digests");
     if (!sizing && n_dsts && !d_caps) throw std::runtime_error("invalid argument: destinations without capacities");
     const uint64_t J = n_dsts;
     std::vector<uint64_t> first_m((size_t)J + 1, 0);
@@ -504,15 +514,43 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     if (rec.status != kIxOk)
         throw DecodeCapacityError("destination " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) + " bytes, too small for " +
                                   std::to_string(counts[rec.bad] * elems[rec.bad]));
+    // the digests' memory, made before anything is launched: the table's columns first | addr | len, the tiles' residues, the digests
+    uint64_t crc_tiles_all = 0;
+    uint64_t* c_cols = nullptr;
+    uint32_t *c_residue = nullptr, *c_crcs = nullptr;
+    if (check) {
+        for (uint64_t j = 0; j < J; j++) crc_tiles_all += crc_tiles((uint64_t)(uintptr_t)d_dsts[j], counts[j] * elems[j]);
+        try {
+            c_cols = own.template alloc<uint64_t>((size_t)J * 3, false);
+            c_residue = own.template alloc<uint32_t>((size_t)crc_tiles_all, false);
+            c_crcs = own.template alloc<uint32_t>((size_t)J, false);
+        } catch (const std::exception&) {
+            throw std::bad_alloc();
+        }
+    }
     decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, p_off, ix.out_len, (uint8_t*)(uintptr_t)base, nullptr, ix.status, 0, 0}, M, slots, own, stats);
     // the merge, queued behind the decode launches on their stream: a plane whose decode failed is merged as whatever staging
     // holds -- bytes of the destination's own size, inside the destination
     if (rec.units) be.launch((size_t)rec.units, PlaneMerge{PlaneTable{p_cols + J, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem, J}, rec.units});
+    if (check) {  // (a destination whose decode failed is digested as whatever it holds: bytes of its own size, inside it)
+        be.launch_waves(1, CrcPlan{p_dsts, p_dsts + 2 * J, p_elems, pieces ? p_elems + J : nullptr, J, ix.out_len, c_cols, c_cols + J, c_cols + 2 * J},
+                        CrcPlan::lds_bytes());
+        crc_launches(be, CrcTable{c_cols, c_cols + J, c_cols + 2 * J, J}, crc_tiles_all, check->d_image, c_residue, c_crcs);
+    }
     std::vector<uint32_t> status((size_t)M);
     be.d2h(status.data(), ix.status, (size_t)M * 4);
     stats.host_waits++;
+    std::vector<uint32_t> got;
+    if (check) {
+        got.resize((size_t)J);
+        be.d2h(got.data(), c_crcs, (size_t)J * 4);
+        stats.host_waits++;
+        if (check->computed) std::memcpy(check->computed, got.data(), (size_t)J * 4);
+    }
     for (uint64_t m = 0; m < M; m++)
         if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
+    for (uint64_t j = 0; j < (check ? J : 0); j++)
+        if (got[j] != check->expect[j]) throw DecodeDigestError(j, check->expect[j], got[j]);
     stats.total_s = be.now() - t0;
 }
 
