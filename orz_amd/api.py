@@ -32,12 +32,42 @@ def _check(rc, what):
         raise OrzError("%s failed (%d): %s" % (what, rc, _native.last_error()))
 
 
-def crc32_buffers(tensors, device=0):
-    """[zlib.crc32 of each tensor's bytes] (orz_crc32_buffers): contiguous tensors of any dtype, all on cuda:`device` -- digested
-    there, where they lie, in three launches and two host waits however many they are -- or all on the CPU."""
+# ---- what the calls on tensors share: each check and each piece of marshalling is written once, here
+def _sync(dev):
+    """the library works on streams of its own: what torch queued on `dev` must be done before a call"""
     import torch
 
-    lib = _native.load()
+    torch.cuda.current_stream(dev).synchronize()
+
+
+def _container(src, dev):
+    """`src` -- a uint8 tensor on `dev` or on the CPU, or bytes-like -- as (keep, on_dev, ptr, n): n bytes at `ptr`, which `keep`
+    keeps alive"""
+    import torch
+
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError("src must be a contiguous uint8 tensor")
+        if src.is_cuda and src.device != dev:
+            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
+        return src, src.is_cuda, (src.data_ptr() if src.numel() else None), src.numel()
+    data = bytes(src)
+    keep = ctypes.create_string_buffer(data, max(len(data), 1))
+    return keep, False, ctypes.cast(keep, ctypes.c_void_p), len(data)
+
+
+def _member_table(members):
+    """`members` -- None, or [(offset, length)] per member -- as (offs, lens, nt) of the decode calls"""
+    if members is None:
+        return None, None, 0
+    nt = len(members)
+    return (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members]), (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members]), nt
+
+
+def _tensor_list(tensors, device):
+    """(cuda:`device`, the tensors as a list, whether they lie on it, their lengths in bytes): contiguous, all there or all on the CPU"""
+    import torch
+
     tensors = list(tensors)
     if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
         raise ValueError("tensors must be contiguous torch tensors")
@@ -45,13 +75,34 @@ def crc32_buffers(tensors, device=0):
     dev = torch.device("cuda", int(device))
     if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
         raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
+    return dev, tensors, on_dev, [t.numel() * t.element_size() for t in tensors]
+
+
+def _uint8_out(out, dev):
+    import torch
+
+    if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
+
+
+def _plane_elems(tensors):
+    elems = [t.element_size() for t in tensors]
+    if any(e > 8 for e in elems):
+        raise ValueError("elements of more than 8 bytes have no byte planes here: view the tensor as a narrower dtype")
+    return elems
+
+
+def crc32_buffers(tensors, device=0):
+    """[zlib.crc32 of each tensor's bytes] (orz_crc32_buffers): contiguous tensors of any dtype, all on cuda:`device` -- digested
+    there, where they lie, in three launches and two host waits however many they are -- or all on the CPU."""
+    lib = _native.load()
+    dev, tensors, on_dev, lengths = _tensor_list(tensors, device)
     n = len(tensors)
-    lengths = [t.numel() * t.element_size() for t in tensors]
     ptrs = (ctypes.c_void_p * max(n, 1))(*[(t.data_ptr() if ln else None) for t, ln in zip(tensors, lengths)])
     lens = (ctypes.c_size_t * max(n, 1))(*lengths)
     crcs = (ctypes.c_uint32 * max(n, 1))()
     if on_dev:
-        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        _sync(dev)
     _check(lib.orz_crc32_buffers(int(device), ptrs, lens, n, 1 if on_dev else 0, crcs), "orz_crc32_buffers")
     return [int(crcs[k]) for k in range(n)]
 
@@ -448,6 +499,30 @@ class MemberEncoder:
         """the digests of the INPUT tensors, taken before the encode: they vouch for the source, not for anything the encoder touched"""
         return crc32_buffers(tensors, device=self._devices[0]) if tensors else []
 
+    def _checked_tensors(self, tensors):
+        if len(self._devices) != 1:
+            raise ValueError("device-resident output needs an encoder on one GPU")
+        return _tensor_list(tensors, self._devices[0])
+
+    def _encode_tensor_list(self, checked, out, digests, n_extra, bound, encode):
+        """What the three encode_tensor* calls do behind their own checks.  `checked`: what _checked_tensors returned; `bound(lengths)`:
+        the bytes of a container that always suffices; `encode(ptrs, lengths, dst_ptr, dst_cap, src_on_device)`: the call on raw
+        addresses, which returns (members, and `n_extra` lists more).  Returns (container, what `encode` returned[, digests])."""
+        import torch
+
+        dev, tensors, on_dev, lengths = checked
+        trim = out is None
+        if trim:
+            out = torch.empty(bound(lengths), dtype=torch.uint8, device=dev)
+        else:
+            _uint8_out(out, dev)
+        if not tensors:
+            return ((out[:0] if trim else out),) + tuple([] for _ in range(1 + n_extra)) + (([],) if digests else ())
+        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
+        _sync(dev)
+        res = encode([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, out.data_ptr(), out.numel(), on_dev)
+        return ((out[: max(o + ln for o, ln in res[0])] if trim else out),) + tuple(res) + crcs
+
     def encode_tensors(self, tensors, out=None, digests=False):
         """One member per tensor of `tensors` (contiguous, any dtype, encoded as their bytes; all on this encoder's GPU or all on
         the CPU), left in device memory: returns (container, members).  `container`: a uint8 tensor on the GPU -- `out` when given,
@@ -455,32 +530,8 @@ class MemberEncoder:
         MemberReader, decode_members_to_device and decode_members_into take as `members=`.  digests=True: the tuple gains a last
         element, [CRC-32 of each input tensor's bytes] (crc32_buffers on the inputs, before the encode): what
         decode_members_into takes as `digests=`."""
-        import torch
-
-        if len(self._devices) != 1:
-            raise ValueError("device-resident output needs an encoder on one GPU")
-        dev = torch.device("cuda", self._devices[0])
-        tensors = list(tensors)
-        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
-            raise ValueError("tensors must be contiguous torch tensors")
-        on_dev = bool(tensors) and tensors[0].is_cuda
-        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
-            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
-        lengths = [t.numel() * t.element_size() for t in tensors]
-        if out is None:
-            out = torch.empty(self.bound_segments(lengths), dtype=torch.uint8, device=dev)
-            trim = True
-        else:
-            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
-            trim = False
-        if not tensors:
-            return ((out[:0] if trim else out), []) + (([],) if digests else ())
-        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
-        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-        members = self.encode_segments_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths,
-                                                 out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return ((out[: max(o + ln for o, ln in members)] if trim else out), members) + crcs
+        return self._encode_tensor_list(self._checked_tensors(tensors), out, digests, 0, self.bound_segments,
+                                        lambda *a: (self.encode_segments_to_device(*a),))
 
     def bound_planes(self, lengths, elems):
         """device bytes that always hold the plane members of segments of these lengths and element sizes
@@ -514,35 +565,10 @@ class MemberEncoder:
         and `out` as for encode_tensors; an element size above 8 raises ValueError.  Returns (container, members, elems):
         `members` [(offset, length)] per plane, `elems` [element size of each tensor]: what decode_planes_into takes.
         digests=True: the tuple gains a last element, [CRC-32 of each input tensor's bytes], as for encode_tensors."""
-        import torch
-
-        if len(self._devices) != 1:
-            raise ValueError("device-resident output needs an encoder on one GPU")
-        dev = torch.device("cuda", self._devices[0])
-        tensors = list(tensors)
-        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
-            raise ValueError("tensors must be contiguous torch tensors")
-        on_dev = bool(tensors) and tensors[0].is_cuda
-        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
-            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
-        elems = [t.element_size() for t in tensors]
-        if any(e > 8 for e in elems):
-            raise ValueError("elements of more than 8 bytes have no byte planes here: view the tensor as a narrower dtype")
-        lengths = [t.numel() * t.element_size() for t in tensors]
-        if out is None:
-            out = torch.empty(self.bound_planes(lengths, elems), dtype=torch.uint8, device=dev)
-            trim = True
-        else:
-            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
-            trim = False
-        if not tensors:
-            return ((out[:0] if trim else out), [], []) + (([],) if digests else ())
-        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
-        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-        members = self.encode_planes_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
-                                               out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return ((out[: max(o + ln for o, ln in members)] if trim else out), members, elems) + crcs
+        checked = self._checked_tensors(tensors)
+        elems = _plane_elems(checked[1])
+        return self._encode_tensor_list(checked, out, digests, 1, lambda lengths: self.bound_planes(lengths, elems),
+                                        lambda ptrs, lengths, *to: (self.encode_planes_to_device(ptrs, lengths, elems, *to), elems))
 
     def bound_planes_pieces(self, lengths, elems, piece_elems):
         """(device bytes that always hold the members, the number of members) of segments of these lengths and element sizes with
@@ -586,38 +612,17 @@ class MemberEncoder:
         Returns (container, members, elems, pieces): `pieces` [pieces per plane of each tensor], what decode_planes_into and
         MemberReader take beside `elems`.  digests=True: the tuple gains a last element, [CRC-32 of each input tensor's bytes],
         as for encode_tensors: a tensor's digest is the same however it is cut."""
-        import torch
-
-        if len(self._devices) != 1:
-            raise ValueError("device-resident output needs an encoder on one GPU")
-        dev = torch.device("cuda", self._devices[0])
-        tensors = list(tensors)
-        if any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tensors):
-            raise ValueError("tensors must be contiguous torch tensors")
-        on_dev = bool(tensors) and tensors[0].is_cuda
-        if any(t.is_cuda != on_dev or (on_dev and t.device != dev) for t in tensors):
-            raise ValueError("tensors must all lie on %s or all on the CPU" % dev)
-        elems = [t.element_size() for t in tensors]
-        if any(e > 8 for e in elems):
-            raise ValueError("elements of more than 8 bytes have no byte planes here: view the tensor as a narrower dtype")
+        checked = self._checked_tensors(tensors)
+        elems = _plane_elems(checked[1])
         piece_elems = int(piece_elems)
         if piece_elems < 0 or piece_elems % 16:
             raise ValueError("the piece size is a multiple of 16 elements")
-        lengths = [t.numel() * t.element_size() for t in tensors]
-        if out is None:
-            out = torch.empty(self.bound_planes_pieces(lengths, elems, piece_elems)[0], dtype=torch.uint8, device=dev)
-            trim = True
-        else:
-            if out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-                raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
-            trim = False
-        if not tensors:
-            return ((out[:0] if trim else out), [], [], []) + (([],) if digests else ())
-        crcs = (self._digests_of(tensors, on_dev),) if digests else ()
-        torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-        members, pieces = self.encode_planes_pieces_to_device([t.data_ptr() if n else 0 for t, n in zip(tensors, lengths)], lengths, elems,
-                                                              piece_elems, out.data_ptr(), out.numel(), src_on_device=on_dev)
-        return ((out[: max(o + ln for o, ln in members)] if trim else out), members, elems, pieces) + crcs
+
+        def encode(ptrs, lengths, *to):
+            members, pieces = self.encode_planes_pieces_to_device(ptrs, lengths, elems, piece_elems, *to)
+            return members, elems, pieces
+
+        return self._encode_tensor_list(checked, out, digests, 2, lambda lengths: self.bound_planes_pieces(lengths, elems, piece_elems)[0], encode)
 
     def close(self):
         if self._h:
@@ -678,27 +683,11 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
 
     lib = _native.load()
     dev = torch.device("cuda", int(device))
-    if isinstance(src, torch.Tensor):
-        if src.dtype != torch.uint8 or not src.is_contiguous():
-            raise ValueError("src must be a contiguous uint8 tensor")
-        if src.is_cuda and src.device != dev:
-            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
-        keep, on_dev = src, src.is_cuda
-        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
-    else:
-        data = bytes(src)
-        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
-        ptr = ctypes.cast(keep, ctypes.c_void_p)
-    if out is not None and (out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous()):
-        raise ValueError("out must be a contiguous uint8 tensor on %s" % dev)
-    if members is None:
-        offs = lens = None
-        nt = 0
-    else:
-        nt = len(members)
-        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
-        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
-    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+    keep, on_dev, ptr, n = _container(src, dev)
+    if out is not None:
+        _uint8_out(out, dev)
+    offs, lens, nt = _member_table(members)
+    _sync(dev)
     dlen, nm = ctypes.c_size_t(), ctypes.c_size_t()
 
     def call(dst, cap, oo, st):
@@ -724,6 +713,60 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
     return tuple(res)
 
 
+def _decode_into(planes, src, outs, device, members, elems, pieces, digests, stats):
+    """decode_members_into (planes False: member k into outs[k]) and decode_planes_into: their checks in one order, the one ABI
+    call that serves the arguments, and that call's own count of host waits"""
+    import torch
+
+    lib = _native.load()
+    dev = torch.device("cuda", int(device))
+    keep, on_dev, ptr, n = _container(src, dev)
+    outs = list(outs)
+    if any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in outs):
+        raise ValueError("outs must be contiguous tensors on %s" % dev)
+    nd = len(outs)
+    el = pc = None
+    if planes:
+        elems = [t.element_size() for t in outs] if elems is None else [int(e) for e in elems]
+        if len(elems) != nd:
+            raise ValueError("one element size per tensor")
+        el = (ctypes.c_uint32 * max(nd, 1))(*[e & 0xFFFFFFFF for e in elems])
+    if pieces is not None:
+        pieces = [int(q) for q in pieces]
+        if len(pieces) != nd or any(q < 0 or q >= 1 << 32 for q in pieces):
+            raise ValueError("one number of pieces per tensor, unsigned 32-bit")
+        pc = (ctypes.c_uint32 * max(nd, 1))(*pieces)
+    offs, lens, nt = _member_table(members)
+    caps = (ctypes.c_size_t * max(nd, 1))(*[t.numel() * t.element_size() for t in outs])
+    dsts = (ctypes.c_void_p * max(nd, 1))(*[(t.data_ptr() if t.numel() else None) for t in outs])
+    sizes = (ctypes.c_size_t * max(nd, 1))()
+    nm = ctypes.c_size_t()
+    st = _native.DecodeStats()
+    if digests is not None:
+        digests, want = _digest_array(digests, nd)
+        got = (ctypes.c_uint32 * max(nd, 1))()
+        name, layout = "orz_decode_tensors_verified", (el, pc, nd, want, sizes, got)
+    elif not planes:
+        name, layout = "orz_decode_members_scatter", (nd, sizes)
+    elif pieces is None:
+        name, layout = "orz_decode_members_planes", (el, nd, sizes)
+    else:
+        name, layout = "orz_decode_members_planes_pieces", (el, pc, nd, sizes)
+    _sync(dev)
+    rc = getattr(lib, name)(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, *layout, ctypes.byref(nm), ctypes.byref(st))
+    if digests is not None:
+        _check_verified(rc, digests, got)
+    else:
+        _check(rc, name)
+    del keep
+    res = [sizes[k] for k in range(nd)]
+    if stats:
+        d = st.as_dict()
+        d["host_waits"] = int(getattr(lib, name + "_host_waits")())
+        return res, d
+    return res
+
+
 def decode_members_into(src, outs, device=0, members=None, stats=False, digests=None):
     """decode members ON THE GPU, member k into the storage of `outs[k]` (orz_decode_members_scatter): no concatenation is made
     and nothing is copied afterwards.  `src` and `members` as for decode_members_to_device; `outs`: contiguous tensors of any
@@ -732,56 +775,7 @@ def decode_members_into(src, outs, device=0, members=None, stats=False, digests=
     tensors overlap.  `digests`: [CRC-32 of each tensor's bytes] (MemberEncoder.encode_tensors(..., digests=True)): the decoded
     bytes are digested on the GPU and held to them (orz_decode_tensors_verified, one host wait more); the first tensor that
     differs raises OrzDigestError.  Returns [decoded size of each member] (and the stats dict, with `host_waits`)."""
-    import torch
-
-    lib = _native.load()
-    dev = torch.device("cuda", int(device))
-    if isinstance(src, torch.Tensor):
-        if src.dtype != torch.uint8 or not src.is_contiguous():
-            raise ValueError("src must be a contiguous uint8 tensor")
-        if src.is_cuda and src.device != dev:
-            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
-        keep, on_dev = src, src.is_cuda
-        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
-    else:
-        data = bytes(src)
-        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
-        ptr = ctypes.cast(keep, ctypes.c_void_p)
-    outs = list(outs)
-    if any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in outs):
-        raise ValueError("outs must be contiguous tensors on %s" % dev)
-    if members is None:
-        offs = lens = None
-        nt = 0
-    else:
-        nt = len(members)
-        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
-        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
-    nd = len(outs)
-    caps = (ctypes.c_size_t * max(nd, 1))(*[t.numel() * t.element_size() for t in outs])
-    dsts = (ctypes.c_void_p * max(nd, 1))(*[(t.data_ptr() if t.numel() else None) for t in outs])
-    sizes = (ctypes.c_size_t * max(nd, 1))()
-    nm = ctypes.c_size_t()
-    st = _native.DecodeStats()
-    if digests is not None:
-        digests, want = _digest_array(digests, nd)
-    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-    if digests is None:
-        rc = lib.orz_decode_members_scatter(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, nd, sizes, ctypes.byref(nm),
-                                            ctypes.byref(st))
-        _check(rc, "orz_decode_members_scatter")
-    else:
-        got = (ctypes.c_uint32 * max(nd, 1))()
-        rc = lib.orz_decode_tensors_verified(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, None, None, nd, want, sizes, got,
-                                             ctypes.byref(nm), ctypes.byref(st))
-        _check_verified(rc, digests, got)
-    del keep
-    res = [sizes[k] for k in range(nd)]
-    if stats:
-        d = st.as_dict()
-        d["host_waits"] = int(lib.orz_decode_members_scatter_host_waits() if digests is None else lib.orz_decode_tensors_verified_host_waits())
-        return res, d
-    return res
+    return _decode_into(False, src, outs, device, members, None, None, digests, stats)
 
 
 def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None, digests=None):
@@ -797,71 +791,7 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     a member table whose entries are mixed up and a piece in the wrong place all decode without an error otherwise; the first
     tensor that differs raises OrzDigestError (.tensor, .expected, .computed), the tensors keeping what was decoded.
     Returns [decoded size of each tensor] (and the stats dict, with `host_waits`)."""
-    import torch
-
-    lib = _native.load()
-    dev = torch.device("cuda", int(device))
-    if isinstance(src, torch.Tensor):
-        if src.dtype != torch.uint8 or not src.is_contiguous():
-            raise ValueError("src must be a contiguous uint8 tensor")
-        if src.is_cuda and src.device != dev:
-            raise ValueError("src lies on %s, not on %s" % (src.device, dev))
-        keep, on_dev = src, src.is_cuda
-        ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
-    else:
-        data = bytes(src)
-        keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
-        ptr = ctypes.cast(keep, ctypes.c_void_p)
-    outs = list(outs)
-    if any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in outs):
-        raise ValueError("outs must be contiguous tensors on %s" % dev)
-    elems = [t.element_size() for t in outs] if elems is None else [int(e) for e in elems]
-    if len(elems) != len(outs):
-        raise ValueError("one element size per tensor")
-    if pieces is not None:
-        pieces = [int(q) for q in pieces]
-        if len(pieces) != len(outs) or any(q < 0 or q >= 1 << 32 for q in pieces):
-            raise ValueError("one number of pieces per tensor, unsigned 32-bit")
-    if members is None:
-        offs = lens = None
-        nt = 0
-    else:
-        nt = len(members)
-        offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
-        lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
-    nd = len(outs)
-    caps = (ctypes.c_size_t * max(nd, 1))(*[t.numel() * t.element_size() for t in outs])
-    dsts = (ctypes.c_void_p * max(nd, 1))(*[(t.data_ptr() if t.numel() else None) for t in outs])
-    el = (ctypes.c_uint32 * max(nd, 1))(*[e & 0xFFFFFFFF for e in elems])
-    sizes = (ctypes.c_size_t * max(nd, 1))()
-    nm = ctypes.c_size_t()
-    st = _native.DecodeStats()
-    if digests is not None:
-        digests, want = _digest_array(digests, nd)
-    torch.cuda.current_stream(dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
-    if digests is not None:
-        pc = None if pieces is None else (ctypes.c_uint32 * max(nd, 1))(*pieces)
-        got = (ctypes.c_uint32 * max(nd, 1))()
-        rc = lib.orz_decode_tensors_verified(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, pc, nd, want, sizes, got,
-                                             ctypes.byref(nm), ctypes.byref(st))
-        _check_verified(rc, digests, got)
-    elif pieces is None:
-        rc = lib.orz_decode_members_planes(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, nd, sizes, ctypes.byref(nm),
-                                           ctypes.byref(st))
-        _check(rc, "orz_decode_members_planes")
-    else:
-        pc = (ctypes.c_uint32 * max(nd, 1))(*pieces)
-        rc = lib.orz_decode_members_planes_pieces(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt, dsts, caps, el, pc, nd, sizes,
-                                                  ctypes.byref(nm), ctypes.byref(st))
-        _check(rc, "orz_decode_members_planes_pieces")
-    del keep
-    res = [sizes[k] for k in range(nd)]
-    if stats:
-        d = st.as_dict()
-        d["host_waits"] = int(lib.orz_decode_tensors_verified_host_waits() if digests is not None else
-                              lib.orz_decode_members_planes_host_waits() if pieces is None else lib.orz_decode_members_planes_pieces_host_waits())
-        return res, d
-    return res
+    return _decode_into(True, src, outs, device, members, elems, pieces, digests, stats)
 
 
 class MemberReader:
@@ -886,25 +816,9 @@ class MemberReader:
         self._h = None
         self._lib = _native.load()
         self._dev = torch.device("cuda", int(device))
-        if isinstance(src, torch.Tensor):
-            if src.dtype != torch.uint8 or not src.is_contiguous():
-                raise ValueError("src must be a contiguous uint8 tensor")
-            if src.is_cuda and src.device != self._dev:
-                raise ValueError("src lies on %s, not on %s" % (src.device, self._dev))
-            keep, on_dev = src, src.is_cuda
-            ptr, n = (src.data_ptr() if src.numel() else None), src.numel()
-        else:
-            data = bytes(src)
-            keep, on_dev, n = ctypes.create_string_buffer(data, max(len(data), 1)), False, len(data)
-            ptr = ctypes.cast(keep, ctypes.c_void_p)
-        if members is None:
-            offs = lens = None
-            nt = 0
-        else:
-            nt = len(members)
-            offs = (ctypes.c_size_t * max(nt, 1))(*[int(o) for o, _ in members])
-            lens = (ctypes.c_size_t * max(nt, 1))(*[int(ln) for _, ln in members])
-        torch.cuda.current_stream(self._dev).synchronize()  # (the library works on streams of its own: what torch queued must be done)
+        keep, on_dev, ptr, n = _container(src, self._dev)
+        offs, lens, nt = _member_table(members)
+        _sync(self._dev)
         self._h = self._lib.orz_reader_open(int(device), ptr, n, 1 if on_dev else 0, offs, lens, nt)
         if not self._h:
             raise OrzError("orz_reader_open failed: %s" % _native.last_error())
@@ -961,8 +875,8 @@ class MemberReader:
 
         if not self._h:
             raise OrzError("the reader is closed")
-        if out is not None and (out.dtype != torch.uint8 or out.device != self._dev or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous uint8 tensor on %s" % self._dev)
+        if out is not None:
+            _uint8_out(out, self._dev)
         ranges = [(int(o), int(ln)) for o, ln in ranges]
         if any(o < 0 or ln < 0 or o >= 1 << 64 or ln >= 1 << 64 for o, ln in ranges):
             raise ValueError("offsets and lengths are unsigned 64-bit numbers")
@@ -974,7 +888,7 @@ class MemberReader:
             want = sum(l for o, l in ranges) if all(o + l <= self.total for o, l in ranges) else 0
             out = torch.empty(want, dtype=torch.uint8, device=self._dev)
         dst = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self._dev)
-        torch.cuda.current_stream(self._dev).synchronize()
+        _sync(self._dev)
         dlen = ctypes.c_uint64()
         st = _native.ReadStats()
         rc = self._lib.orz_reader_read(self._h, off, ln, nr, ctypes.c_void_p(dst.data_ptr()), out.numel(), ctypes.byref(dlen),
@@ -1028,8 +942,8 @@ class MemberReader:
 
         if not self._h:
             raise OrzError("the reader is closed")
-        if out is not None and (out.dtype != torch.uint8 or out.device != self._dev or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous uint8 tensor on %s" % self._dev)
+        if out is not None:
+            _uint8_out(out, self._dev)
         ranges = [(int(j), int(f), int(c)) for j, f, c in ranges]
         if any(v < 0 or v >= 1 << 64 for r in ranges for v in r):
             raise ValueError("tensor numbers, first elements and counts are unsigned 64-bit numbers")
@@ -1043,7 +957,7 @@ class MemberReader:
             ok = all(j < len(t) and f + c <= t[j][0] for j, f, c in ranges)
             out = torch.empty(sum(c * t[j][1] for j, f, c in ranges) if ok else 0, dtype=torch.uint8, device=self._dev)
         dst = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self._dev)
-        torch.cuda.current_stream(self._dev).synchronize()
+        _sync(self._dev)
         dlen = ctypes.c_uint64()
         st = _native.ReadStats()
         rc = self._lib.orz_reader_read_elements(self._h, tj, tf, tc, nr, ctypes.c_void_p(dst.data_ptr()), out.numel(), ctypes.byref(dlen),

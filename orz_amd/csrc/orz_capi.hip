@@ -86,6 +86,36 @@ int mapped(F&& f) {
     }
 }
 
+// The four decodes into a list of destinations (scatter, planes, pieces, verified) around their drivers: `waits`, the entry's own
+// thread-local count of host waits, answers for this call from here on; `bad`, the entry's own argument check, and the device are
+// refused; run(be, members, st) drives a backend of the call's own; the member count is stored however the call ends, the
+// stats when it succeeds.
+template <class Run>
+int decode_into_list(uint64_t& waits, bool bad, int device, size_t* n_members_out, orz_decode_stats* stats, Run&& run) {
+    waits = 0;
+    if (bad) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    uint64_t members = 0;
+    orz::DecodeScatterStats st;
+    const int rc = mapped([&] {
+        orz::HipBackend be(device);
+        run(be, members, st);
+    });
+    waits = st.host_waits;
+    if (n_members_out) *n_members_out = (size_t)members;
+    if (rc == ORZ_OK) put_stats(stats, st);
+    return rc;
+}
+// `bytes` (or none) handed to the caller as a malloc'ed buffer, released with orz_free
+int give_bytes(const std::vector<uint8_t>& bytes, uint8_t** dst, size_t* dst_len) {
+    uint8_t* p = (uint8_t*)std::malloc(bytes.size() ? bytes.size() : 1);
+    if (!p) return fail(ORZ_ENOMEM, "malloc failed");
+    if (!bytes.empty()) std::memcpy(p, bytes.data(), bytes.size());
+    *dst = p;
+    *dst_len = bytes.size();
+    return ORZ_OK;
+}
+
 using Enc = orz::StreamEncoder<orz::HipBackend>;
 
 // parse mode of a new encoder: the GPU-native fast mode unless ORZ_MODE=exact asks for the reference-identical parse
@@ -800,6 +830,18 @@ const char* segment_items(const orz_members* m, const void* const* seg_src, cons
     for (size_t k = 0; k < n_segs; k++) items[k] = MemberItem{(const uint8_t*)seg_src[k], seg_len[k]};
     return nullptr;
 }
+// ORZ_OK when the members of `segs` can go to the caller's device buffer, else ORZ_EINVAL with the reason as the thread's message:
+// what the calls with a device-resident output check last, behind their own checks and the answer for no segments
+int device_output_check(const orz_members* m, const std::vector<MemberItem>& segs, int src_on_device, const uint8_t* d_dst, size_t d_cap,
+                        const size_t* offs, const size_t* lens) {
+    if (!d_dst || !offs || !lens) return fail(ORZ_EINVAL, "bad argument");
+    if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
+    if (src_on_device)
+        for (size_t k = 0; k < segs.size(); k++)
+            if (segs[k].len && d_cap && segs[k].p < d_dst + d_cap && d_dst < segs[k].p + segs[k].len)
+                return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
+    return ORZ_OK;
+}
 }  // namespace
 int orz_members_encode(orz_members* m, const void* src, size_t n, int src_on_device, size_t member_bytes, uint8_t** dst,
                        size_t* dst_len, size_t* n_members_out) {
@@ -843,13 +885,7 @@ int orz_members_encode_segments(orz_members* m, const void* const* seg_src, cons
     try {
         std::vector<MemberItem> items;
         if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, items)) return fail(ORZ_EINVAL, why);
-        if (!n_segs) {  // no members, no bytes, nothing launched
-            uint8_t* p = (uint8_t*)std::malloc(1);
-            if (!p) return fail(ORZ_ENOMEM, "malloc failed");
-            *dst = p;
-            *dst_len = 0;
-            return ORZ_OK;
-        }
+        if (!n_segs) return give_bytes({}, dst, dst_len);  // no members, no bytes, nothing launched
         size_t in_total = 0;
         for (const MemberItem& it : items) in_total += it.len;
         const size_t want = std::min(orz_members_bound_segments(seg_len, n_segs), in_total / 2 + n_segs * 65536 + (32u << 20));
@@ -864,12 +900,7 @@ int orz_members_encode_segments_to_device(orz_members* m, const void* const* seg
         std::vector<MemberItem> items;
         if (const char* why = segment_items(m, seg_src, seg_len, n_segs, src_on_device, items)) return fail(ORZ_EINVAL, why);
         if (!n_segs) return ORZ_OK;
-        if (!d_dst || !offs || !lens) return fail(ORZ_EINVAL, "bad argument");
-        if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
-        if (src_on_device)
-            for (size_t k = 0; k < n_segs; k++)
-                if (items[k].len && d_cap && items[k].p < d_dst + d_cap && d_dst < items[k].p + items[k].len)
-                    return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
+        if (const int rc = device_output_check(m, items, src_on_device, d_dst, d_cap, offs, lens)) return rc;
         return members_encode_device(m, items, src_on_device, d_dst, d_cap, offs, lens);
     } catch (const std::exception& e) {
         return fail(ORZ_ENOMEM, e.what());
@@ -908,12 +939,7 @@ int encode_planes_pieces(orz_members* m, const void* const* seg_src, const size_
                                             std::to_string(seg_elem[k]));
         }
         if (!n_segs) return ORZ_OK;
-        if (!d_dst || !offs || !lens) return fail(ORZ_EINVAL, "bad argument");
-        if (!one_device(m)) return fail(ORZ_EINVAL, "device-resident output needs all workers on one device");
-        if (src_on_device)
-            for (size_t k = 0; k < n_segs; k++)
-                if (segs[k].len && d_cap && segs[k].p < d_dst + d_cap && d_dst < segs[k].p + segs[k].len)
-                    return fail(ORZ_EINVAL, "segment " + std::to_string(k) + " overlaps the output buffer");
+        if (const int rc = device_output_check(m, segs, src_on_device, d_dst, d_cap, offs, lens)) return rc;
         // the staging buffer's layout: table | per segment, at multiples of 256: [its upload] [its planes]
         size_t n_rows = 0, n_items = 0;
         for (size_t k = 0; k < n_segs; k++) {
@@ -1024,11 +1050,7 @@ int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* 
                 [&](const uint8_t* buf, size_t k) { out.insert(out.end(), buf, buf + k); }, [](bool, size_t, size_t) {});
             members++;
         }
-        uint8_t* p = (uint8_t*)std::malloc(out.size() ? out.size() : 1);
-        if (!p) return fail(ORZ_ENOMEM, "malloc failed");
-        std::memcpy(p, out.data(), out.size());
-        *dst = p;
-        *dst_len = out.size();
+        if (const int rc = give_bytes(out, dst, dst_len)) return rc;
         if (n_members_out) *n_members_out = members;
         return ORZ_OK;
     } catch (const std::exception& e) {
@@ -1045,11 +1067,7 @@ int orz_decode_members_device(int device, const uint8_t* src, size_t n, uint8_t*
         std::vector<uint8_t> out;
         orz::DecodeStats st;
         orz::decode_members_device(be, src, n, out, st, decode_slots());
-        uint8_t* p = (uint8_t*)std::malloc(out.size() ? out.size() : 1);
-        if (!p) return fail(ORZ_ENOMEM, "malloc failed");
-        std::memcpy(p, out.data(), out.size());
-        *dst = p;
-        *dst_len = out.size();
+        if (const int rc = give_bytes(out, dst, dst_len)) return rc;
         if (n_members_out) *n_members_out = (size_t)st.members;
         put_stats(stats, st);
         return ORZ_OK;
@@ -1090,21 +1108,12 @@ thread_local uint64_t g_scatter_waits = 0;
 int orz_decode_members_scatter(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
                                size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, size_t n_dsts, size_t* out_lens,
                                size_t* n_members_out, orz_decode_stats* stats) {
-    g_scatter_waits = 0;
-    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps)) return fail(ORZ_EINVAL, "bad argument");
-    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
-    uint64_t members = 0;
-    orz::DecodeScatterStats st;
-    const int rc = mapped([&] {
-        orz::HipBackend be(device);
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps);
+    return decode_into_list(g_scatter_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
         orz::decode_members_scatter(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs,
                                     (const uint64_t*)lens, n_members, d_dsts, (const uint64_t*)d_caps, n_dsts, (uint64_t*)out_lens, members, st,
                                     decode_slots());
     });
-    g_scatter_waits = st.host_waits;
-    if (n_members_out) *n_members_out = (size_t)members;
-    if (rc == ORZ_OK) put_stats(stats, st);
-    return rc;
 }
 uint64_t orz_decode_members_scatter_host_waits(void) { return g_scatter_waits; }
 
@@ -1112,20 +1121,11 @@ thread_local uint64_t g_planes_waits = 0;
 int orz_decode_members_planes(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
                               size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, size_t n_dsts,
                               size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats) {
-    g_planes_waits = 0;
-    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && !elems)) return fail(ORZ_EINVAL, "bad argument");
-    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
-    uint64_t members = 0;
-    orz::DecodeScatterStats st;
-    const int rc = mapped([&] {
-        orz::HipBackend be(device);
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && !elems);
+    return decode_into_list(g_planes_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
         orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
                                    n_members, d_dsts, (const uint64_t*)d_caps, elems, n_dsts, (uint64_t*)out_lens, members, st, decode_slots());
     });
-    g_planes_waits = st.host_waits;
-    if (n_members_out) *n_members_out = (size_t)members;
-    if (rc == ORZ_OK) put_stats(stats, st);
-    return rc;
 }
 uint64_t orz_decode_members_planes_host_waits(void) { return g_planes_waits; }
 
@@ -1133,22 +1133,13 @@ thread_local uint64_t g_pieces_waits = 0;
 int orz_decode_members_planes_pieces(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
                                      size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems,
                                      const uint32_t* pieces, size_t n_dsts, size_t* out_lens, size_t* n_members_out, orz_decode_stats* stats) {
-    g_pieces_waits = 0;
-    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && (!elems || !pieces))) return fail(ORZ_EINVAL, "bad argument");
-    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
-    uint64_t members = 0;
-    orz::DecodeScatterStats st;
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && (!elems || !pieces));
     static const uint32_t none = 0;  // (no destinations: still "with pieces")
-    const int rc = mapped([&] {
-        orz::HipBackend be(device);
+    return decode_into_list(g_pieces_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
         orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
                                    n_members, d_dsts, (const uint64_t*)d_caps, elems, n_dsts, (uint64_t*)out_lens, members, st, decode_slots(),
                                    pieces ? pieces : &none);
     });
-    g_pieces_waits = st.host_waits;
-    if (n_members_out) *n_members_out = (size_t)members;
-    if (rc == ORZ_OK) put_stats(stats, st);
-    return rc;
 }
 uint64_t orz_decode_members_planes_pieces_host_waits(void) { return g_pieces_waits; }
 
@@ -1197,23 +1188,14 @@ thread_local uint64_t g_verified_waits = 0;
 int orz_decode_tensors_verified(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens, size_t n_members,
                                 uint8_t* const* d_dsts, const size_t* d_caps, const uint32_t* elems, const uint32_t* pieces, size_t n_dsts,
                                 const uint32_t* crcs, size_t* out_lens, uint32_t* out_crcs, size_t* n_members_out, orz_decode_stats* stats) {
-    g_verified_waits = 0;
-    if ((!src && n) || (!offs != !lens) || (d_dsts && n_dsts && (!d_caps || !crcs))) return fail(ORZ_EINVAL, "bad argument");
-    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
-    uint64_t members = 0;
-    orz::DecodeScatterStats st;
-    const int rc = mapped([&] {
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && (!d_caps || !crcs));
+    return decode_into_list(g_verified_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
         const std::vector<uint32_t> ones(elems ? 0 : n_dsts + 1, 1);  // (no element sizes: bytes, the scatter layout)
-        orz::HipBackend be(device);
         const orz::CrcCheck check{d_dsts ? crc_device_image(device) : nullptr, crcs, out_crcs};
         orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
                                    n_members, d_dsts, (const uint64_t*)d_caps, elems ? elems : ones.data(), n_dsts, (uint64_t*)out_lens, members, st,
                                    decode_slots(), pieces, &check);
     });
-    g_verified_waits = st.host_waits;
-    if (n_members_out) *n_members_out = (size_t)members;
-    if (rc == ORZ_OK) put_stats(stats, st);
-    return rc;
 }
 uint64_t orz_decode_tensors_verified_host_waits(void) { return g_verified_waits; }
 int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {

@@ -676,8 +676,7 @@ void decode_members_device(BE& be, const uint8_t* src, size_t n, std::vector<uin
         be.d2h(status.data(), d_status, (size_t)M * 4);
         be.d2h(out.data(), d_out, ix.out_total);
     }  // (the buffers go here: their release counts into total_s, as it always did)
-    for (uint32_t m = 0; m < M; m++)
-        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
+    throw_first_bad(status.data(), M);
     stats.total_s = be.now() - t0;
 }
 

@@ -5,14 +5,19 @@
 // ::read_cached (orz_decode_range.h).
 // Here is what is literally the same in all of them: the message of a failed member, the owner of a call's device buffers, the
 // upload of a host container, the timing bracket, the loop over rounds of `slots` members and the launch of one round -- and
-// decode_all, the whole sequence of the four one-shot drivers.  What differs stays with its driver: where the bytes go, how the
-// statuses come back, and the readers' rules for zeroing a state that outlives the call.
+// decode_all, the whole sequence of the four one-shot drivers.  The three drivers with destinations in device memory (to_device,
+// scatter, planes) also open the same way -- open_container: upload, index, host waits, the stats' sizes -- and the two with a
+// destination per member or tensor close the same way -- read_statuses, one read and one wait; throw_first_bad -- and refuse the same
+// destinations, each in its own words (check_destinations, DestinationNames).  What differs stays with its driver: where the bytes
+// go, what is read back besides the statuses, and the readers' rules for zeroing a state that outlives the call.
 //
 // orz_decode_device.h includes this header below the decoder's types; include that one.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace orz {
@@ -49,6 +54,58 @@ const uint8_t* upload_container(DeviceBuffers<BE>& own, const uint8_t* src, size
     own.be.h2d(up, src, n);
     host_waits++;
     return up;
+}
+
+// The opening of a driver with destinations in device memory: the container where the kernels read it, `ix` (a DeviceIndex,
+// orz_decode_index.h) built over it -- `want_arrays` as for its build() --, the host waits of both counted, `members` and the stats'
+// sizes set.  Returns the container's device address.  What build() throws passes through, with only the upload's wait counted.
+template <class BE, class IX, class Stats>
+const uint8_t* open_container(DeviceBuffers<BE>& own, IX& ix, const uint8_t* src, size_t n, bool src_on_device, bool table, const uint64_t* offs,
+                              const uint64_t* lens, size_t n_table, bool want_arrays, uint64_t& members, Stats& stats) {
+    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
+    ix.build(d_src, n, table, offs, lens, n_table, want_arrays);
+    stats.host_waits += ix.host_waits;
+    members = ix.members;
+    stats.members = ix.members; stats.in_bytes = n; stats.out_bytes = ix.total;
+    return d_src;
+}
+
+// The closing: the M statuses behind the last launch, in one read and one host wait ...
+template <class BE>
+std::vector<uint32_t> read_statuses(BE& be, const uint32_t* d_status, uint64_t M, uint64_t& host_waits) {
+    std::vector<uint32_t> status((size_t)M);
+    be.d2h(status.data(), d_status, (size_t)M * 4);
+    host_waits++;
+    return status;
+}
+// ... and decode_status_error for the first member whose status is not kDecOk
+inline void throw_first_bad(const uint32_t* status, uint64_t M) {
+    for (uint64_t m = 0; m < M; m++)
+        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
+}
+
+// How a driver speaks of its destinations: "no destination for member 3" or "no destination 3 for its planes", "the destination of
+// member 3" or "destination 3", "the destinations of members 2 and 5" or "destinations 2 and 5".
+struct DestinationNames {
+    const char *missing, *missing_end, *one, *two;
+};
+// The destinations that have bytes -- `iv`: (address, index) in index order, sorted here; caps[index]: their capacities -- may be
+// written: none null, none wrapping the address space, none overlapping the next (whole capacities count), none overlapping a
+// device-resident container.  Throws std::runtime_error for the first that may not, a null one before any other.
+inline void check_destinations(std::vector<std::pair<uint64_t, uint64_t>>& iv, const uint64_t* caps, const uint8_t* src, size_t n, bool src_on_device,
+                               const DestinationNames& names) {
+    const auto refuse = [](const std::string& what) { return std::runtime_error("invalid argument: " + what); };
+    for (const auto& d : iv)
+        if (!d.first) throw refuse(names.missing + std::to_string(d.second) + names.missing_end);
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 0; i < iv.size(); i++) {
+        const uint64_t a = iv[i].first, k = iv[i].second, cap = caps[k];
+        if (cap > ~a) throw refuse(names.one + std::to_string(k) + " wraps the address space");
+        if (i + 1 < iv.size() && iv[i + 1].first < a + cap)
+            throw refuse(names.two + std::to_string(std::min(k, iv[i + 1].second)) + " and " + std::to_string(std::max(k, iv[i + 1].second)) + " overlap");
+        const uint64_t s = (uint64_t)(uintptr_t)src;
+        if (src_on_device && n && cap && a < s + n && s < a + cap) throw refuse(std::string("the container and ") + names.one + std::to_string(k) + " overlap");
+    }
 }
 
 // Event timing on from here to the end of the scope, also when the scope is left by an exception.  finish() waits for the

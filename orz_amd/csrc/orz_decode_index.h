@@ -287,14 +287,10 @@ void decode_members_to_device(BE& be, const uint8_t* src, size_t n, bool src_on_
     if (src_on_device && n && d_cap && (const uint8_t*)d_dst < src + n && src < (const uint8_t*)d_dst + d_cap)
         throw std::runtime_error("invalid argument: the container and the output buffer overlap");
     DeviceBuffers<BE> own(be);  // the uploaded container and the decoder's state
-    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
     DeviceIndex<BE> ix(be);
-    ix.build(d_src, n, table, offs, lens, n_table, !sizing || out_offs != nullptr);
-    stats.host_waits += ix.host_waits;
-    const uint64_t M = ix.members;
+    const uint8_t* d_src = open_container(own, ix, src, n, src_on_device, table, offs, lens, n_table, !sizing || out_offs != nullptr, members, stats);
+    const uint64_t M = members;
     dst_len = ix.total;
-    members = M;
-    stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
     if (!sizing && d_cap < ix.total)
         throw DecodeCapacityError("output buffer of " + std::to_string(d_cap) + " bytes is too small for " + std::to_string(ix.total));
     if (!sizing && M)
@@ -307,11 +303,7 @@ void decode_members_to_device(BE& be, const uint8_t* src, size_t n, bool src_on_
         be.d2h(back.data() + from, (const uint8_t*)ix.out_off + from, to - from);
         stats.host_waits++;
         if (out_offs) std::memcpy(out_offs, back.data(), (size_t)M * 8);
-        if (want_status) {
-            const uint32_t* status = (const uint32_t*)(back.data() + (size_t)M * 8);
-            for (uint64_t m = 0; m < M; m++)
-                if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
-        }
+        if (want_status) throw_first_bad((const uint32_t*)(back.data() + (size_t)M * 8), M);
     }
     stats.total_s = be.now() - t0;
 }

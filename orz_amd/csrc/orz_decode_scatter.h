@@ -101,13 +101,9 @@ void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_de
     const bool sizing = d_dsts == nullptr;
     if (!sizing && n_dsts && !d_caps) throw std::runtime_error("invalid argument: destinations without capacities");
     DeviceBuffers<BE> own(be);  // the uploaded container, the plan and the decoder's state
-    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
     DeviceIndex<BE> ix(be);
-    ix.build(d_src, n, table, offs, lens, n_table, true);
-    stats.host_waits += ix.host_waits;
-    const uint64_t M = ix.members;
-    members = M;
-    stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
+    const uint8_t* d_src = open_container(own, ix, src, n, src_on_device, table, offs, lens, n_table, true, members, stats);
+    const uint64_t M = members;
     if (sizing) {
         const uint64_t k = std::min<uint64_t>(M, out_lens ? n_dsts : 0);
         if (k) {
@@ -155,31 +151,14 @@ void decode_members_scatter(BE& be, const uint8_t* src, size_t n, bool src_on_de
     if (out_lens) std::copy(sizes, sizes + M, out_lens);
     // the destinations of members that have bytes, by address: none null, none inside another, none inside the container
     std::vector<std::pair<uint64_t, uint64_t>> iv;  // (address, member)
-    for (uint64_t m = 0; m < M; m++) {
-        if (!sizes[m]) continue;
-        if (!d_dsts[m]) throw std::runtime_error("invalid argument: no destination for member " + std::to_string(m));
-        iv.emplace_back((uint64_t)(uintptr_t)d_dsts[m], m);
-    }
-    std::sort(iv.begin(), iv.end());
-    for (size_t i = 0; i < iv.size(); i++) {
-        const uint64_t a = iv[i].first, m = iv[i].second, cap = d_caps[m];
-        if (cap > ~a) throw std::runtime_error("invalid argument: the destination of member " + std::to_string(m) + " wraps the address space");
-        if (i + 1 < iv.size() && iv[i + 1].first < a + cap)
-            throw std::runtime_error("invalid argument: the destinations of members " + std::to_string(std::min(m, iv[i + 1].second)) + " and " +
-                                     std::to_string(std::max(m, iv[i + 1].second)) + " overlap");
-        const uint64_t s = (uint64_t)(uintptr_t)src;
-        if (src_on_device && n && cap && a < s + n && s < a + cap)
-            throw std::runtime_error("invalid argument: the container and the destination of member " + std::to_string(m) + " overlap");
-    }
+    for (uint64_t m = 0; m < M; m++)
+        if (sizes[m]) iv.emplace_back((uint64_t)(uintptr_t)d_dsts[m], m);
+    check_destinations(iv, d_caps, src, n, src_on_device, DestinationNames{"no destination for member ", "", "the destination of member ", "the destinations of members "});
     if (rec.status != kIxOk)
         throw DecodeCapacityError("the destination of member " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) +
                                   " bytes, too small for " + std::to_string(sizes[rec.bad]));
     decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, ix.out_off, ix.out_len, out, nullptr, ix.status, 0, 0}, M, slots, own, stats);
-    std::vector<uint32_t> status((size_t)M);
-    be.d2h(status.data(), ix.status, (size_t)M * 4);
-    stats.host_waits++;
-    for (uint64_t m = 0; m < M; m++)
-        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
+    throw_first_bad(read_statuses(be, ix.status, M, stats.host_waits).data(), M);
     stats.total_s = be.now() - t0;
 }
 

@@ -418,13 +418,9 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         staged = staged || elems[j] > 1;
     }
     DeviceBuffers<BE> own(be);  // the uploaded container, the plan, the staging buffer and the decoder's state
-    const uint8_t* d_src = upload_container(own, src, n, src_on_device, stats.host_waits);
     DeviceIndex<BE> ix(be);
-    ix.build(d_src, n, table, offs, lens, n_table, true);
-    stats.host_waits += ix.host_waits;
-    const uint64_t M = ix.members;
-    members = M;
-    stats.members = M; stats.in_bytes = n; stats.out_bytes = ix.total;
+    const uint8_t* d_src = open_container(own, ix, src, n, src_on_device, table, offs, lens, n_table, true, members, stats);
+    const uint64_t M = members;
     if (first_m[J] != M)
         throw std::runtime_error("invalid argument: " + std::to_string(first_m[J]) + (pieces ? " pieces of planes for " : " planes for ") +
                                  std::to_string(M) + " members");
@@ -495,22 +491,9 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     sizes_of(sizes);
     // the destinations that have bytes, by address: none null, none inside another, none inside the container
     std::vector<std::pair<uint64_t, uint64_t>> iv;  // (address, destination)
-    for (uint64_t j = 0; j < J; j++) {
-        if (!counts[j]) continue;
-        if (!d_dsts[j]) throw std::runtime_error("invalid argument: no destination " + std::to_string(j) + " for its planes");
-        iv.emplace_back((uint64_t)(uintptr_t)d_dsts[j], j);
-    }
-    std::sort(iv.begin(), iv.end());
-    for (size_t i = 0; i < iv.size(); i++) {
-        const uint64_t a = iv[i].first, j = iv[i].second, cap = d_caps[j];
-        if (cap > ~a) throw std::runtime_error("invalid argument: destination " + std::to_string(j) + " wraps the address space");
-        if (i + 1 < iv.size() && iv[i + 1].first < a + cap)
-            throw std::runtime_error("invalid argument: destinations " + std::to_string(std::min(j, iv[i + 1].second)) + " and " +
-                                     std::to_string(std::max(j, iv[i + 1].second)) + " overlap");
-        const uint64_t s = (uint64_t)(uintptr_t)src;
-        if (src_on_device && n && cap && a < s + n && s < a + cap)
-            throw std::runtime_error("invalid argument: the container and destination " + std::to_string(j) + " overlap");
-    }
+    for (uint64_t j = 0; j < J; j++)
+        if (counts[j]) iv.emplace_back((uint64_t)(uintptr_t)d_dsts[j], j);
+    check_destinations(iv, d_caps, src, n, src_on_device, DestinationNames{"no destination ", " for its planes", "destination ", "destinations "});
     if (rec.status != kIxOk)
         throw DecodeCapacityError("destination " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) + " bytes, too small for " +
                                   std::to_string(counts[rec.bad] * elems[rec.bad]));
@@ -537,9 +520,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
                         CrcPlan::lds_bytes());
         crc_launches(be, CrcTable{c_cols, c_cols + J, c_cols + 2 * J, J}, crc_tiles_all, check->d_image, c_residue, c_crcs);
     }
-    std::vector<uint32_t> status((size_t)M);
-    be.d2h(status.data(), ix.status, (size_t)M * 4);
-    stats.host_waits++;
+    const std::vector<uint32_t> status = read_statuses(be, ix.status, M, stats.host_waits);
     std::vector<uint32_t> got;
     if (check) {
         got.resize((size_t)J);
@@ -547,8 +528,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         stats.host_waits++;
         if (check->computed) std::memcpy(check->computed, got.data(), (size_t)J * 4);
     }
-    for (uint64_t m = 0; m < M; m++)
-        if (status[m] != kDecOk) throw decode_status_error(m, status[m]);
+    throw_first_bad(status.data(), M);
     for (uint64_t j = 0; j < (check ? J : 0); j++)
         if (got[j] != check->expect[j]) throw DecodeDigestError(j, check->expect[j], got[j]);
     stats.total_s = be.now() - t0;
