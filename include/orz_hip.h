@@ -450,6 +450,49 @@ uint64_t orz_decode_tensors_verified_host_waits(void);
  * rounded up to 16, both on `device` and owned by the caller -- between two events after one warming launch; *ms = milliseconds
  * a launch. */
 int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms);
+/* DELTAS: tensors as the planes (and pieces) of tensor XOR base, merged with the base on the device.  For a tensor kept many
+ * times with small differences -- step N and step N + 1 of a run, a fine-tune beside its base model -- when the reader already
+ * holds the other one: the steps of a bf16 run shrink 2.3 to 6 times against their plain planes, a frozen layer costs almost
+ * nothing.  XOR is its own inverse and works byte by byte, so it needs no rule per dtype and commutes with the split
+ * into planes and pieces.  The container format does not change: every member is an ordinary orz stream, and WHICH tensors are
+ * deltas, and of what, travels beside the container as elems, pieces and the digests do.  The base comes in where every byte
+ * is touched once anyway, in the move between interleaved bytes and planes: no temporary of the tensor's size, no pass more.
+ * orz_members_encode_deltas_to_device: orz_members_encode_planes_pieces_to_device word for word -- layout, pieces_out, bounds
+ *   (orz_members_bound_planes_pieces still suffices), refusals -- with seg_base (n_segs entries): seg_base[k] = seg_len[k] bytes
+ *   resident where the sources are (src_on_device governs both), elements of seg_elem[k] bytes, or NULL for no base.  Every
+ *   member's stream is byte for byte what that call writes for the bytes src XOR base as a segment of their own; with no base
+ *   anywhere the output is that call's byte for byte.  Host bases are uploaded into the call's one staging buffer beside their
+ *   segments; still ONE table upload (the bases are a column of it), ONE split launch (PlaneSplitDelta) and one wait before the
+ *   workers start.  A segment with seg_elem == 1 that has a base is staged like the others; without one a device-resident one
+ *   is encoded where it lies, as there.  Neither the sources nor the bases are written.  ORZ_EINVAL in addition: a NULL
+ *   seg_base with n_segs > 0.
+ * orz_decode_tensors_delta: the contract of orz_decode_tensors_verified -- elems and pieces optional in the same way -- with
+ *   these differences.  crcs may be NULL: nothing is verified, and launches and waits are those of
+ *   orz_decode_members_planes_pieces.  With crcs: verification, the order of the verdicts and ORZ_EBADMSG as there; the digests
+ *   are of the RESTORED tensors, not of the deltas, so a delta applied to another base than the one it was made of is a digest
+ *   mismatch.  d_bases (n_dsts entries; NULL with n_dsts > 0 is ORZ_EINVAL, "bad argument"): d_bases[j] = out_lens[j] bytes on
+ *   `device`, the base of destination j, or NULL for none.  A base may be EXACTLY its own destination's address (in place): the
+ *   destination holds the base on entry and the tensor on return.  ORZ_EINVAL before any decode launch, with nothing written
+ *   anywhere, each naming the destination: a base that wraps the address space, one that overlaps its own destination at any
+ *   other address, one that overlaps another destination (whole capacities count).  A base may overlap the container or another
+ *   base: all of them are only read.  The bases go up in the plan's ONE upload and ONE PlaneMergeDelta launch stands where
+ *   PlaneMerge stood (a destination with elems == 1 that has a base is staged and merged too): host waits are exactly those of
+ *   orz_decode_members_planes_pieces for the same container, plus 1 with crcs.  AFTER A FAILURE behind the launches -- payload
+ *   damage (ORZ_EINVAL naming the member) or a digest mismatch -- a base given out of place is untouched, and a destination
+ *   decoded in place holds NEITHER its base NOR its tensor: keep a copy of a base you cannot make again.
+ * orz_decode_tensors_delta_host_waits: the host waits of the calling thread's last such call.
+ * orz_plane_delta_move_time: orz_plane_move_time for PlaneSplitDelta / PlaneMergeDelta with the base at d_base (count x elem
+ *   bytes on `device`); elem may be 1 too.  A measuring hook (tools/dev/delta_bench.py), not a data path. */
+int orz_members_encode_deltas_to_device(orz_members*, const void* const* seg_src, const void* const* seg_base, const size_t* seg_len,
+                                        const uint32_t* seg_elem, size_t n_segs, size_t piece_elems, int src_on_device, uint8_t* d_dst,
+                                        size_t d_cap, size_t* offs, size_t* lens, size_t* pieces_out);
+int orz_decode_tensors_delta(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                             size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const void* const* d_bases,
+                             const uint32_t* elems, const uint32_t* pieces, size_t n_dsts, const uint32_t* crcs, size_t* out_lens,
+                             uint32_t* out_crcs, size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_tensors_delta_host_waits(void);
+int orz_plane_delta_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge,
+                              int reps, double* ms);
 
 /* ---- byte ranges of a members container (orz_decode_range.h) ------------------------------------------
  * A reader indexes a container ONCE (on the device, as orz_decode_members_to_device does) and then serves reads of byte

@@ -918,9 +918,13 @@ namespace {
 // pieces to a plane of `count` elements at a piece size of `piece_elems` (0: never cut)
 size_t plane_pieces(size_t count, size_t piece_elems) { return piece_elems && piece_elems < count ? (count + piece_elems - 1) / piece_elems : 1; }
 
-// orz_members_encode_planes_pieces_to_device; pieces_out == nullptr and piece_elems == 0: orz_members_encode_planes_to_device
+// orz_members_encode_planes_pieces_to_device; pieces_out == nullptr and piece_elems == 0: orz_members_encode_planes_to_device;
+// seg_base not null: orz_members_encode_deltas_to_device -- seg_base[k] = segment k's base, resident where the sources are, or
+// nullptr for none.  A segment that has a base and bytes is a row of the split whatever its element size, its base one more
+// column of the table's ONE upload, and the ONE launch is PlaneSplitDelta; with no base anywhere the call is the pieces call.
 int encode_planes_pieces(orz_members* m, const void* const* seg_src, const size_t* seg_len, const uint32_t* seg_elem, size_t n_segs,
-                         size_t piece_elems, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens, size_t* pieces_out) {
+                         size_t piece_elems, int src_on_device, uint8_t* d_dst, size_t d_cap, size_t* offs, size_t* lens, size_t* pieces_out,
+                         const void* const* seg_base = nullptr) {
     struct Staging {  // the call's one device buffer: the descriptor table, then the planes (and the uploads of host segments)
         void* p = nullptr;
         ~Staging() { if (p) (void)hipFree(p); }
@@ -940,20 +944,25 @@ int encode_planes_pieces(orz_members* m, const void* const* seg_src, const size_
         }
         if (!n_segs) return ORZ_OK;
         if (const int rc = device_output_check(m, segs, src_on_device, d_dst, d_cap, offs, lens)) return rc;
-        // the staging buffer's layout: table | per segment, at multiples of 256: [its upload] [its planes]
+        // the staging buffer's layout: table [| base column] | per segment, at multiples of 256: [its upload] [its base's upload] [its planes]
+        const auto base_of = [&](size_t k) { return seg_base && segs[k].len ? (const uint8_t*)seg_base[k] : nullptr; };
         size_t n_rows = 0, n_items = 0;
+        bool deltas = false;
         for (size_t k = 0; k < n_segs; k++) {
             const size_t Q = plane_pieces(segs[k].len / seg_elem[k], piece_elems);
-            n_rows += seg_elem[k] > 1;
+            n_rows += seg_elem[k] > 1 || base_of(k);
+            deltas = deltas || base_of(k);
             n_items += seg_elem[k] * Q;
             if (pieces_out) pieces_out[k] = Q;
         }
         const auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
-        size_t at = up256(orz::plane_table_bytes(n_rows));
-        std::vector<size_t> raw_at(n_segs, 0), planes_at(n_segs, 0);
+        const size_t bases_at = orz::plane_table_bytes(n_rows);  // (a multiple of 8)
+        size_t at = up256(bases_at + (deltas ? n_rows * 8 : 0));
+        std::vector<size_t> raw_at(n_segs, 0), base_at(n_segs, 0), planes_at(n_segs, 0);
         for (size_t k = 0; k < n_segs; k++) {
             if (!src_on_device && segs[k].len) { raw_at[k] = at; at = up256(at + segs[k].len); }
-            if (seg_elem[k] > 1 && segs[k].len) { planes_at[k] = at; at = up256(at + (size_t)seg_elem[k] * orz::plane_pitch(segs[k].len / seg_elem[k])); }
+            if (!src_on_device && base_of(k)) { base_at[k] = at; at = up256(at + segs[k].len); }
+            if ((seg_elem[k] > 1 || base_of(k)) && segs[k].len) { planes_at[k] = at; at = up256(at + (size_t)seg_elem[k] * orz::plane_pitch(segs[k].len / seg_elem[k])); }
         }
         const bool need = n_rows || !src_on_device;
         orz::HipBackend& be = *m->workers[0]->be;
@@ -971,34 +980,44 @@ int encode_planes_pieces(orz_members* m, const void* const* seg_src, const size_
         items.reserve(n_items);
         std::vector<orz::PlaneRow> rows;
         rows.reserve(n_rows);
+        std::vector<uint64_t> row_base;  // the rows' bases
+        row_base.reserve(n_rows);
         for (size_t k = 0; k < n_segs; k++) {
             const uint32_t e = seg_elem[k];
             const size_t count = segs[k].len / e;
             const uint8_t* d_seg = segs[k].p;
+            const uint8_t* d_base = base_of(k);
             if (!src_on_device && segs[k].len) {
                 be.h2d(stage + raw_at[k], segs[k].p, segs[k].len);
                 d_seg = stage + raw_at[k];
+            }
+            if (!src_on_device && d_base) {
+                be.h2d(stage + base_at[k], d_base, segs[k].len);
+                d_base = stage + base_at[k];
             }
             // plane p's pieces: its bytes [q P, min(count, (q + 1) P)), an item each (P a multiple of 16: each starts as aligned as the plane)
             const size_t Q = plane_pieces(count, piece_elems), P = Q > 1 ? piece_elems : count;
             const auto cut = [&](const uint8_t* plane) {
                 for (size_t q = 0; q < Q; q++) items.push_back(MemberItem{count ? plane + q * P : nullptr, std::min(P, count - q * P)});
             };
-            if (e == 1) {
+            if (e == 1 && !d_base) {
                 cut(d_seg);
                 continue;
             }
             const size_t pitch = orz::plane_pitch(count);
             for (uint32_t p = 0; p < e; p++) cut(stage + planes_at[k] + p * pitch);
             rows.push_back(orz::PlaneRow{(uint64_t)(uintptr_t)d_seg, (uint64_t)(uintptr_t)(stage + planes_at[k]), count, e});
+            row_base.push_back((uint64_t)(uintptr_t)d_base);
         }
         if (!rows.empty()) {
             std::vector<uint64_t> image;
             uint64_t units = 0;
             const orz::PlaneTable t = orz::plane_table_image(rows, stage, image, units);
+            if (deltas) image.insert(image.end(), row_base.begin(), row_base.end());  // (image ends at bases_at)
             if (units) {
                 be.h2d(stage, image.data(), image.size() * 8);
-                be.launch((size_t)units, orz::PlaneSplit{t, units});
+                if (deltas) be.launch((size_t)units, orz::PlaneSplitDelta{t, (const uint64_t*)(stage + bases_at), units});
+                else be.launch((size_t)units, orz::PlaneSplit{t, units});
                 be.sync();  // (the workers read the planes on streams of their own)
             }
         }
@@ -1031,6 +1050,14 @@ int orz_members_encode_planes_pieces_to_device(orz_members* m, const void* const
                                                size_t* lens, size_t* pieces_out) {
     if (n_segs && !pieces_out) return fail(ORZ_EINVAL, "bad argument");
     return encode_planes_pieces(m, seg_src, seg_len, seg_elem, n_segs, piece_elems, src_on_device, d_dst, d_cap, offs, lens, pieces_out);
+}
+int orz_members_encode_deltas_to_device(orz_members* m, const void* const* seg_src, const void* const* seg_base, const size_t* seg_len,
+                                        const uint32_t* seg_elem, size_t n_segs, size_t piece_elems, int src_on_device, uint8_t* d_dst,
+                                        size_t d_cap, size_t* offs, size_t* lens, size_t* pieces_out) {
+    if (n_segs && (!pieces_out || !seg_base)) return fail(ORZ_EINVAL, "bad argument");
+    static const void* const none = nullptr;  // (no segments: still "with bases")
+    return encode_planes_pieces(m, seg_src, seg_len, seg_elem, n_segs, piece_elems, src_on_device, d_dst, d_cap, offs, lens, pieces_out,
+                                seg_base ? seg_base : &none);
 }
 int orz_decode_members_mem(const uint8_t* src, size_t n, uint8_t** dst, size_t* dst_len, size_t* n_members_out) {
     if ((!src && n) || !dst || !dst_len) return fail(ORZ_EINVAL, "bad argument");
@@ -1198,8 +1225,38 @@ int orz_decode_tensors_verified(int device, const void* src, size_t n, int src_o
     });
 }
 uint64_t orz_decode_tensors_verified_host_waits(void) { return g_verified_waits; }
+
+thread_local uint64_t g_delta_waits = 0;
+int orz_decode_tensors_delta(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens, size_t n_members,
+                             uint8_t* const* d_dsts, const size_t* d_caps, const void* const* d_bases, const uint32_t* elems, const uint32_t* pieces,
+                             size_t n_dsts, const uint32_t* crcs, size_t* out_lens, uint32_t* out_crcs, size_t* n_members_out, orz_decode_stats* stats) {
+    static_assert(sizeof(void*) == sizeof(uint64_t), "the bases are handed to the device as 64-bit words");
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps) || (n_dsts && !d_bases);
+    static const uint64_t none = 0;  // (no destinations: still "with bases")
+    return decode_into_list(g_delta_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
+        const std::vector<uint32_t> ones(elems ? 0 : n_dsts + 1, 1);  // (no element sizes: bytes, a member per destination)
+        const orz::CrcCheck check{d_dsts && crcs ? crc_device_image(device) : nullptr, crcs, out_crcs};
+        orz::decode_members_planes(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
+                                   n_members, d_dsts, (const uint64_t*)d_caps, elems ? elems : ones.data(), n_dsts, (uint64_t*)out_lens, members, st,
+                                   decode_slots(), pieces, crcs ? &check : nullptr, d_bases ? (const uint64_t*)d_bases : &none);
+    });
+}
+uint64_t orz_decode_tensors_delta_host_waits(void) { return g_delta_waits; }
+namespace {
+int plane_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms);
+}
 int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {
     if (!d_inter || !d_planes || !count || !ms || reps < 1 || (elem != 2 && elem != 4 && elem != 8)) return fail(ORZ_EINVAL, "bad argument");
+    return plane_move_time(device, d_inter, nullptr, d_planes, count, elem, merge, reps, ms);
+}
+int orz_plane_delta_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge, int reps,
+                              double* ms) {
+    if (!d_inter || !d_base || !d_planes || !count || !ms || reps < 1 || !orz::plane_elem_ok(elem)) return fail(ORZ_EINVAL, "bad argument");
+    return plane_move_time(device, d_inter, d_base, d_planes, count, elem, merge, reps, ms);
+}
+namespace {
+// d_base == nullptr: the plain kernels; else the delta kernels with that base
+int plane_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms) {
     if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
     struct Events {
         hipEvent_t a = nullptr, b = nullptr;
@@ -1209,16 +1266,20 @@ int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count,
         orz::HipBackend be(device);
         orz::DeviceBuffers<orz::HipBackend> own(be);
         std::vector<orz::PlaneRow> rows{orz::PlaneRow{(uint64_t)(uintptr_t)d_inter, (uint64_t)(uintptr_t)d_planes, count, elem}};
-        uint8_t* d_table = own.alloc<uint8_t>(orz::plane_table_bytes(1), false);
+        uint8_t* d_table = own.alloc<uint8_t>(orz::plane_table_bytes(1) + 8, false);  // (the table, then the base column)
         std::vector<uint64_t> image;
         uint64_t units = 0;
         const orz::PlaneTable t = orz::plane_table_image(rows, d_table, image, units);
+        image.push_back((uint64_t)(uintptr_t)d_base);
+        const uint64_t* d_bases = (const uint64_t*)(d_table + orz::plane_table_bytes(1));
         be.h2d(d_table, image.data(), image.size() * 8);
         ORZ_HIP_CHECK(hipEventCreate(&ev.a));
         ORZ_HIP_CHECK(hipEventCreate(&ev.b));
         for (int r = -1; r < reps; r++) {  // (the first launch warms up)
             if (r == 0) ORZ_HIP_CHECK(hipEventRecord(ev.a, be.stream()));
-            if (merge) be.launch((size_t)units, orz::PlaneMerge{t, units});
+            if (d_base && merge) be.launch((size_t)units, orz::PlaneMergeDelta{t, d_bases, units});
+            else if (d_base) be.launch((size_t)units, orz::PlaneSplitDelta{t, d_bases, units});
+            else if (merge) be.launch((size_t)units, orz::PlaneMerge{t, units});
             else be.launch((size_t)units, orz::PlaneSplit{t, units});
         }
         ORZ_HIP_CHECK(hipEventRecord(ev.b, be.stream()));
@@ -1231,6 +1292,7 @@ int orz_plane_move_time(int device, void* d_inter, void* d_planes, size_t count,
         return fail(ORZ_ENODEV, e.what());
     }
 }
+}  // namespace
 
 // ------------------------------------------------------------------------------ byte ranges of a container
 struct orz_reader {

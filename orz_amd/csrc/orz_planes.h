@@ -26,6 +26,10 @@
 // tensor's members are plane-major: plane 0's pieces 0 .. Q - 1, then plane 1's.  The format does not change -- a piece is a
 // member -- and neither do split and merge: a plane's pieces lie and decode back to back in the plane's place in staging.  The
 // driver takes pieces[j], the pieces per plane of destination j, beside elems[j]; without them every plane is one piece.
+//
+// DELTAS.  A tensor may be kept as the planes (and pieces) of tensor XOR base, the base being a tensor the reader already holds:
+// PlaneSplitDelta / PlaneMergeDelta are the two moves with a column of base addresses, and the driver takes bases[j] beside
+// elems[j] and pieces[j].  Nothing in the format says so: which tensors are deltas, and of what, travels beside the container.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -214,6 +218,138 @@ struct PlaneMerge {
     ORZ_HD void operator()(size_t u) const { plane_move_unit<true>(t, units, (uint64_t)u); }
 };
 
+// ------------------------------------------------------------------------------------------------ deltas against base tensors
+// PlaneSplitDelta / PlaneMergeDelta are PlaneSplit / PlaneMerge with one more column: base[j], the address of a BASE tensor's
+// interleaved bytes -- as many bytes as tensor j has, elements of the same size -- or 0 for none.  The split writes the planes of
+// tensor XOR base, the merge writes planes XOR base: XOR is its own inverse, works byte by byte and commutes with the move, so the
+// move between interleaved bytes and planes, which touches every byte once anyway, is where the base comes in.  An element size
+// of 1 is a row here too (with a base its bytes are XORed on their way; the plain kernels have no such rows).  A row without a
+// base moves as the plain kernels move it.  A full unit whose interleaved address, base address, plane address and pitch are
+// all multiples of 16: e 16-byte loads of the tensor's (merge: the planes') bytes and e of the base's, ALL issued before the
+// first store, the XOR on the 4 e dwords of the interleaved side -- before the shuffle in the split, behind it in the merge --
+// and e 16-byte stores; every other unit goes byte by byte, each byte read just before it is written.  No LDS, no scratch, no
+// atomics, and the rule of DESIGN 2a: a lane reads and writes its own unit only.  That makes the merge safe IN PLACE, base[j] ==
+// the interleaved address: the lane has loaded its base bytes before it stores over them, and no other lane reads them.  The
+// split never writes the padding behind a plane's count, the source or the base.
+// The bodies are their own, not plane_move_unit with a parameter more: the plain kernels keep their code and registers.
+
+// the split's shuffle alone, in registers: the 16 E interleaved bytes (w) into 16 bytes of each of E planes (pl)
+template <int E>
+ORZ_HD void plane_split_shuffle(const uint32_t (&w)[4 * E], uint32_t (&pl)[4 * E]) {
+    if constexpr (E == 1) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) pl[k] = w[k];
+    } else if constexpr (E == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            pl[k] = plane_perm(w[2 * k + 1], w[2 * k], 0x06040200u);
+            pl[4 + k] = plane_perm(w[2 * k + 1], w[2 * k], 0x07050301u);
+        }
+    } else {
+        constexpr int S = E / 4;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int h = 0; h < S; h++)
+                plane_transpose4(w[S * (4 * k) + h], w[S * (4 * k + 1) + h], w[S * (4 * k + 2) + h], w[S * (4 * k + 3) + h], pl[4 * (4 * h) + k],
+                                 pl[4 * (4 * h + 1) + k], pl[4 * (4 * h + 2) + k], pl[4 * (4 * h + 3) + k]);
+    }
+}
+// One full unit with a base, all three sides at multiples of 16.
+template <int E, bool kMerge>
+ORZ_HD void plane_unit_delta(uint8_t* inter, const uint8_t* base, uint8_t* plane, uint64_t pitch) {
+    uint32_t w[4 * E], b[4 * E], pl[4 * E];
+    if constexpr (kMerge) {
+#pragma unroll
+        for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, plane + (uint64_t)p * pitch);
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_load16(b + 4 * q, base + 16 * q);
+        if constexpr (E == 1) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = pl[k];
+        } else {
+            plane_merge_shuffle<E>(pl, w);
+        }
+#pragma unroll
+        for (int k = 0; k < 4 * E; k++) w[k] ^= b[k];
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_store16(inter + 16 * q, w + 4 * q);
+    } else {
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_load16(w + 4 * q, inter + 16 * q);
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_load16(b + 4 * q, base + 16 * q);
+#pragma unroll
+        for (int k = 0; k < 4 * E; k++) w[k] ^= b[k];
+        plane_split_shuffle<E>(w, pl);
+#pragma unroll
+        for (int p = 0; p < E; p++) plane_store16(plane + (uint64_t)p * pitch, pl + 4 * p);
+    }
+}
+
+// work unit u of the table with the base column `bases` ([t.n] addresses, 0 = none)
+template <bool kMerge>
+ORZ_HD void plane_move_unit_delta(const PlaneTable& t, const uint64_t* bases, uint64_t units, uint64_t u) {
+    if (u >= units || !t.n) return;
+    const uint64_t j = last_at_or_below(t.first, t.n, u);
+    const uint64_t at = (u - t.first[j]) * kPlaneUnit, count = t.count[j];  // the unit's first element
+    if (at >= count) return;
+    const uint32_t e = t.elem[j];
+    const uint64_t pitch = t.pitch[j], left = count - at, b0 = bases[j];
+    uint8_t* const inter = (uint8_t*)(uintptr_t)t.inter[j] + at * e;
+    uint8_t* const plane = (uint8_t*)(uintptr_t)t.plane0[j] + at;
+    const bool quads = left >= kPlaneUnit && ((t.inter[j] | t.plane0[j] | pitch | b0) & 15) == 0;
+    if (!b0) {  // no base: as the plain kernels move it
+        if (quads && (e == 2 || e == 4 || e == 8)) {
+            if (kMerge) {
+                if (e == 2) plane_unit_merge<2>(inter, plane, pitch);
+                else if (e == 4) plane_unit_merge<4>(inter, plane, pitch);
+                else plane_unit_merge<8>(inter, plane, pitch);
+            } else {
+                if (e == 2) plane_unit_split<2>(inter, plane, pitch);
+                else if (e == 4) plane_unit_split<4>(inter, plane, pitch);
+                else plane_unit_split<8>(inter, plane, pitch);
+            }
+            return;
+        }
+        const uint32_t k = left < kPlaneUnit ? (uint32_t)left : kPlaneUnit;
+        for (uint32_t p = 0; p < e; p++)
+            for (uint32_t i = 0; i < k; i++) {
+                if (kMerge) inter[(uint64_t)i * e + p] = plane[(uint64_t)p * pitch + i];
+                else plane[(uint64_t)p * pitch + i] = inter[(uint64_t)i * e + p];
+            }
+        return;
+    }
+    const uint8_t* const base = (const uint8_t*)(uintptr_t)b0 + at * e;
+    if (quads && (e == 1 || e == 2 || e == 4 || e == 8)) {
+        if (e == 1) plane_unit_delta<1, kMerge>(inter, base, plane, pitch);
+        else if (e == 2) plane_unit_delta<2, kMerge>(inter, base, plane, pitch);
+        else if (e == 4) plane_unit_delta<4, kMerge>(inter, base, plane, pitch);
+        else plane_unit_delta<8, kMerge>(inter, base, plane, pitch);
+        return;
+    }
+    const uint32_t k = left < kPlaneUnit ? (uint32_t)left : kPlaneUnit;
+    for (uint32_t p = 0; p < e; p++)
+        for (uint32_t i = 0; i < k; i++) {  // (in place the base byte IS the byte written: read first)
+            const uint64_t a = (uint64_t)i * e + p;
+            if (kMerge) inter[a] = (uint8_t)(plane[(uint64_t)p * pitch + i] ^ base[a]);
+            else plane[(uint64_t)p * pitch + i] = (uint8_t)(inter[a] ^ base[a]);
+        }
+}
+
+struct PlaneSplitDelta {
+    PlaneTable t;
+    const uint64_t* base;  // [t.n] the bases' addresses (0: none)
+    uint64_t units;
+    ORZ_HD void operator()(size_t u) const { plane_move_unit_delta<false>(t, base, units, (uint64_t)u); }
+};
+struct PlaneMergeDelta {
+    PlaneTable t;
+    const uint64_t* base;
+    uint64_t units;
+    ORZ_HD void operator()(size_t u) const { plane_move_unit_delta<true>(t, base, units, (uint64_t)u); }
+};
+
 // One tensor of a table the HOST makes (the encode side, where every size is known before anything is launched).
 struct PlaneRow {
     uint64_t inter, plane0, count;
@@ -291,6 +427,11 @@ uint64_t plane_piece_count(const char* what, uint64_t j, uint64_t f, uint32_t e,
 // plane_stage_at still leaves room when first_m counts pieces: the e Q members of destination j decode to e count bytes, so
 // its successor's place lies at least e count + 32 e Q - 15 bytes behind its own, and e planes of pitch <= count + 15 end
 // e count + 15 e bytes behind it -- 15 e + 15 <= 32 e Q for every Q >= 1; likewise the last one ends inside plane_stage_bound.
+// DELTAS (`bases` not null; null for every other caller, for whom nothing here changes): bases[j] is the address of destination
+// j's base, 0 for none.  A single-byte destination that has one cannot be decoded where it lies -- its bytes have to pass the
+// merge, which XORs the base in -- so it is staged like the multi-byte ones: its members point at its place in staging, its
+// units are plane_units(count) and its row has its count.  The room plane_stage_at leaves still suffices for e = 1: the
+// inequality above reads 30 <= 32 Q.
 struct PlanePlan {
     const uint64_t* dsts;     // [n_dsts] the destinations' addresses
     const uint64_t* caps;     // [n_dsts] their capacities
@@ -308,6 +449,7 @@ struct PlanePlan {
     uint64_t* units;          // [n_dsts] out: the merge's units of the destination (0 for an element size of 1)
     uint64_t *t_inter, *t_plane0, *t_pitch, *t_count;  // [n_dsts] out: the merge's table but for its first-unit column
     uint32_t* t_elem;
+    const uint64_t* bases = nullptr;  // [n_dsts] the bases' addresses (0: none), or nullptr: no deltas
     ORZ_HD void operator()(size_t m) const {
         if (m >= members) return;
         const uint64_t j = last_at_or_below(first_m, n_dsts, (uint64_t)m);
@@ -316,15 +458,16 @@ struct PlanePlan {
         const uint32_t e = elems[j], len = out_len[m];
         const uint64_t S = out_len[f], count = (Q - 1) * S + out_len[f + Q - 1], pitch = plane_pitch(count);
         const uint64_t at = stage + plane_stage_at(ix_off[f], f);
-        out_off[m] = (e == 1 ? dsts[j] : at + p * pitch) + q * S - base;
+        const bool direct = e == 1 && !(bases && bases[j]);  // decoded where it lies, no row in the merge
+        out_off[m] = (direct ? dsts[j] : at + p * pitch) + q * S - base;
         sizes[m] = len;
         if (r) return;
         verdict[j] = count > ~(uint64_t)0 / e || caps[j] < count * e ? kPlShortDestination : (uint32_t)kIxOk;
-        units[j] = e == 1 ? 0 : plane_units(count);
+        units[j] = direct ? 0 : plane_units(count);
         t_inter[j] = dsts[j];
         t_plane0[j] = at;
         t_pitch[j] = pitch;
-        t_count[j] = e == 1 ? 0 : count;
+        t_count[j] = direct ? 0 : count;
         t_elem[j] = e;
     }
 };
@@ -366,6 +509,32 @@ struct PlaneScan {
     }
 };
 
+// The bases of a delta decode may be read while the destinations are written.  `iv`: the destinations that have bytes as
+// check_destinations left them, sorted by address and disjoint; bases[j]: the address of destination j's base (0: none), as
+// many bytes as the destination's size, counts[j] x elems[j].  Throws std::runtime_error for the first destination, in index
+// order, whose base wraps the address space, overlaps its own destination at another address than the destination's own (in
+// place), or overlaps another destination's capacity.
+inline void check_bases(const std::vector<std::pair<uint64_t, uint64_t>>& iv, const uint64_t* caps, const uint64_t* bases,
+                        const std::vector<uint64_t>& counts, const uint32_t* elems) {
+    const auto refuse = [](const std::string& what) { return std::runtime_error("invalid argument: " + what); };
+    std::vector<uint64_t> dst_of(counts.size(), 0);
+    for (const auto& d : iv) dst_of[(size_t)d.second] = d.first;
+    for (uint64_t j = 0; j < counts.size(); j++) {
+        const uint64_t b = bases[j], len = counts[j] * elems[j];
+        if (!b || !len) continue;
+        const std::string who = "the base of destination " + std::to_string(j);
+        if (len > ~b) throw refuse(who + " wraps the address space");
+        if (b == dst_of[(size_t)j]) continue;  // in place: inside its own destination, which overlaps no other
+        // the destinations that begin below the base's end, from the last one down: their ends ascend with their addresses
+        auto it = std::lower_bound(iv.begin(), iv.end(), std::make_pair(b + len, (uint64_t)0));
+        if (it != iv.begin()) {
+            const auto& d = *(it - 1);
+            if (d.first + caps[d.second] > b)
+                throw refuse(who + " overlaps destination " + std::to_string(d.second) + (d.second == j ? " at another address than its own" : ""));
+        }
+    }
+}
+
 // Decodes the members of `src` (n / src_on_device / table / offs / lens / n_table as for decode_members_scatter) into n_dsts
 // destinations in device memory: destination j, d_caps[j] bytes at d_dsts[j], takes the next elems[j] members as the byte planes
 // of elements of elems[j] bytes (1, 2, 4 or 8) -- with `pieces`, the next elems[j] x pieces[j] members, pieces[j] to a plane,
@@ -396,11 +565,23 @@ struct PlaneScan {
 // above; otherwise the first destination whose digest differs throws DecodeDigestError.  check->computed (when not null) is
 // filled whenever the digest launches ran.  A sizing call verifies nothing; no digests for destinations is refused before any
 // launch, and so is memory for the digests that cannot be had (std::bad_alloc).
+// DELTAS (`bases` not null; null for every other caller, for whom nothing here changes): the members hold the planes of tensor XOR
+// base, and bases[j] is the address of destination j's base in device memory -- as many bytes as the destination's size -- or 0 for
+// none.  The bases go up as one more column of the plan's ONE upload, and that uploaded column is the merge's base column (the
+// merge's rows are the destinations): ONE PlaneMergeDelta launch stands where PlaneMerge stood and XORs the bases in.  Launches
+// and host waits are those of the same call without bases.  A base may BE its destination (the same address): the destination
+// holds the base on entry and the tensor on return.  A destination of single bytes that has a base is staged (PlanePlan).  The
+// digests of a verified call are the restored tensors', so a delta applied to another base is a digest mismatch.
+// Refused in addition, before any decode launch, each naming the destination: a base that wraps the address space, one that
+// overlaps its own destination at another address, one that overlaps another destination (whole capacities count).  Bases are
+// only read: one may overlap the container or another base.  A base of a destination of no bytes is not looked at.
+// After payload damage or a digest mismatch a base given out of place is untouched; a destination decoded in place holds
+// neither its base nor its tensor.
 template <class BE>
 void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_device, bool table, const uint64_t* offs, const uint64_t* lens,
                            size_t n_table, uint8_t* const* d_dsts, const uint64_t* d_caps, const uint32_t* elems, size_t n_dsts,
                            uint64_t* out_lens, uint64_t& members, DecodeScatterStats& stats, uint32_t slots = 2048,
-                           const uint32_t* pieces = nullptr, const CrcCheck* check = nullptr) {
+                           const uint32_t* pieces = nullptr, const CrcCheck* check = nullptr, const uint64_t* bases = nullptr) {
     const double t0 = be.now();
     const bool sizing = d_dsts == nullptr;
     if (n_dsts && !elems) throw std::runtime_error("invalid argument: destinations without element sizes");
@@ -415,7 +596,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
                                      " bytes (1, 2, 4 or 8)");
         if (pieces && !pieces[j]) throw std::runtime_error("invalid argument: destination " + std::to_string(j) + " has no pieces");
         first_m[j + 1] = first_m[j] + (uint64_t)elems[j] * (pieces ? pieces[j] : 1);
-        staged = staged || elems[j] > 1;
+        staged = staged || elems[j] > 1 || (bases && bases[j]);
     }
     DeviceBuffers<BE> own(be);  // the uploaded container, the plan, the staging buffer and the decoder's state
     DeviceIndex<BE> ix(be);
@@ -453,25 +634,28 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
         }
         if (!stage) throw std::bad_alloc();
     }
-    // the plan's memory, u64 columns first: dsts | caps | first_m | (ONE upload up to here, with elems and pieces at its end) out_off[M] |
+    // the plan's memory, u64 columns first: dsts | caps | first_m | bases (of a delta call) | (ONE upload up to here, with elems and pieces at its end) out_off[M] |
     // units | table: first, inter, plane0, pitch, count | then u32: elems | table elem | verdict | sizes[M] | the record; sizes
     // and record are read back together
-    const size_t up_words = (size_t)J * 3 + ((size_t)J * (pieces ? 2 : 1) + 1) / 2;
+    const size_t up_cols = bases ? 4 : 3;
+    const size_t up_words = (size_t)J * up_cols + ((size_t)J * (pieces ? 2 : 1) + 1) / 2;
     std::vector<uint64_t> up(up_words, 0);
     uint64_t base = (uint64_t)(uintptr_t)stage;
     for (uint64_t j = 0; j < J; j++) {
         up[j] = (uint64_t)(uintptr_t)d_dsts[j];
         up[J + j] = d_caps[j];
         up[2 * J + j] = first_m[j];
+        if (bases) up[3 * J + j] = bases[j];
         if (!base) base = up[j];
     }
-    std::memcpy(up.data() + 3 * J, elems, (size_t)J * 4);
-    if (pieces) std::memcpy((uint32_t*)(up.data() + 3 * J) + J, pieces, (size_t)J * 4);
+    std::memcpy(up.data() + up_cols * J, elems, (size_t)J * 4);
+    if (pieces) std::memcpy((uint32_t*)(up.data() + up_cols * J) + J, pieces, (size_t)J * 4);
     const size_t off_at = up_words * 8, cols_at = off_at + (size_t)M * 8, u32_at = cols_at + (size_t)J * 6 * 8;
     const size_t sizes_at = u32_at + (size_t)J * 8, rec_at = (sizes_at + (size_t)M * 4 + 7) / 8 * 8;
     uint8_t* plan = own.template alloc<uint8_t>(rec_at + sizeof(PlaneRecord), false);
     uint64_t* p_dsts = (uint64_t*)plan;
-    uint32_t* p_elems = (uint32_t*)(p_dsts + 3 * J);
+    uint32_t* p_elems = (uint32_t*)(p_dsts + up_cols * J);
+    const uint64_t* p_bases = bases ? p_dsts + 3 * J : nullptr;
     uint64_t* p_off = (uint64_t*)(plan + off_at);
     uint64_t* p_cols = (uint64_t*)(plan + cols_at);  // units | first | inter | plane0 | pitch | count
     uint32_t* p_telem = (uint32_t*)(plan + u32_at);
@@ -480,7 +664,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     be.h2d(plan, up.data(), up_words * 8);
     stats.host_waits++;
     be.launch(M, PlanePlan{p_dsts, p_dsts + J, p_dsts + 2 * J, p_elems, pieces ? p_elems + J : nullptr, J, ix.out_off, ix.out_len, M, base, (uint64_t)(uintptr_t)stage, p_off, p_sizes,
-                           p_verdict, p_cols, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem});
+                           p_verdict, p_cols, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem, p_bases});
     be.launch_waves(1, PlaneScan{p_cols, p_verdict, p_cols + J, J, (PlaneRecord*)(plan + rec_at)}, PlaneScan::lds_bytes());
     std::vector<uint8_t> back(rec_at + sizeof(PlaneRecord) - sizes_at);
     be.d2h(back.data(), plan + sizes_at, back.size());
@@ -494,6 +678,7 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     for (uint64_t j = 0; j < J; j++)
         if (counts[j]) iv.emplace_back((uint64_t)(uintptr_t)d_dsts[j], j);
     check_destinations(iv, d_caps, src, n, src_on_device, DestinationNames{"no destination ", " for its planes", "destination ", "destinations "});
+    if (bases) check_bases(iv, d_caps, bases, counts, elems);
     if (rec.status != kIxOk)
         throw DecodeCapacityError("destination " + std::to_string(rec.bad) + " holds " + std::to_string(d_caps[rec.bad]) + " bytes, too small for " +
                                   std::to_string(counts[rec.bad] * elems[rec.bad]));
@@ -514,7 +699,9 @@ void decode_members_planes(BE& be, const uint8_t* src, size_t n, bool src_on_dev
     decode_all(be, DecodeArgs{d_src, ix.begin, ix.end, p_off, ix.out_len, (uint8_t*)(uintptr_t)base, nullptr, ix.status, 0, 0}, M, slots, own, stats);
     // the merge, queued behind the decode launches on their stream: a plane whose decode failed is merged as whatever staging
     // holds -- bytes of the destination's own size, inside the destination
-    if (rec.units) be.launch((size_t)rec.units, PlaneMerge{PlaneTable{p_cols + J, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem, J}, rec.units});
+    const PlaneTable merge_t{p_cols + J, p_cols + 2 * J, p_cols + 3 * J, p_cols + 4 * J, p_cols + 5 * J, p_telem, J};
+    if (rec.units && bases) be.launch((size_t)rec.units, PlaneMergeDelta{merge_t, p_bases, rec.units});
+    else if (rec.units) be.launch((size_t)rec.units, PlaneMerge{merge_t, rec.units});
     if (check) {  // (a destination whose decode failed is digested as whatever it holds: bytes of its own size, inside it)
         be.launch_waves(1, CrcPlan{p_dsts, p_dsts + 2 * J, p_elems, pieces ? p_elems + J : nullptr, J, ix.out_len, c_cols, c_cols + J, c_cols + 2 * J},
                         CrcPlan::lds_bytes());
