@@ -603,9 +603,35 @@ int orz_reader_cache_stats(orz_reader*, orz_cache_stats* stats);
  *   ranges exactly as above, but decodes ONLY THE PIECES a range touches, each only as far as the furthest element asked inside
  *   it, all of them side by side: the last rows of a tensor cost its last pieces, not the tensor.  orz_read_stats means what it
  *   means above, so members_decoded counts pieces; cursors work per member, so pieces are hit, resumed, fresh or uncached as any
- *   member; the host waits stay 3 and 2. */
+ *   member; the host waits stay 3 and 2.
+ * orz_reader_set_bases: the container holds DELTAS (orz_members_encode_deltas_to_device: the planes of tensor XOR base), and
+ *   bases[j] is tensor j's base -- counts[j] x elems[j] bytes of device memory on the reader's device, as orz_reader_tensor_info
+ *   reports them -- or NULL for none.  orz_reader_read_elements then returns RESTORED elements, planes XOR base, of the tensors
+ *   that have a base, and the elements of the others as before.  n_tensors must be the number of tensors declared; n_tensors == 0
+ *   withdraws the bases, and so does every successful orz_reader_set_planes / orz_reader_set_planes_pieces (a refused one leaves
+ *   them).  The bases are BORROWED until they are withdrawn or the reader is closed, and only read: a base may overlap the
+ *   container or another base.  The base of a tensor of no elements is not looked at.  ORZ_EINVAL with nothing changed: no
+ *   declaration, n_tensors different from the tensors declared ("X bases for Y tensors"), bases == NULL with n_tensors > 0, a
+ *   base whose bytes wrap the address space (the tensor is named).  Nothing is launched and the host does not wait; cursors are
+ *   kept -- they hold planes and know nothing of bases --, so the same range read against another base decodes nothing anew.
+ * orz_reader_read_elements WITH BASES: when a range that has elements names a tensor with a base, the ranges' base slices go up
+ *   as one more column of the read's one upload and the launch that ends the read makes the XOR (ElementGatherDelta): no
+ *   temporary, the same launches and the same host waits as the read without bases; a read none of whose non-empty ranges names
+ *   such a tensor is the read without bases in every respect.  The base slice of range k -- count[k] x e bytes from bases[tensor[k]]
+ *   + first[k] x e -- must be disjoint from ALL the bytes the read writes, [d_dst, d_dst + *dst_len), or BEGIN EXACTLY WHERE RANGE
+ *   k's OWN BYTES GO: the read IN PLACE, the slice holding the base's elements on entry and the restored ones on return.  Any
+ *   other overlap is ORZ_EINVAL naming the range, before anything reaches the device: the slice would be overwritten by, or
+ *   overwrite, another range (two equal ranges cannot both be read in place).  After payload damage a slice read in place holds
+ *   neither the base nor the tensor; a base given out of place is never written. */
 int orz_reader_set_planes(orz_reader*, const uint32_t* elems, size_t n_tensors);
 int orz_reader_set_planes_pieces(orz_reader*, const uint32_t* elems, const uint32_t* pieces, size_t n_tensors);
+int orz_reader_set_bases(orz_reader*, const void* const* bases, size_t n_tensors);
+/* orz_element_gather_time: the launch that ends ONE whole-tensor element read, alone: `count` elements (a multiple of 16) of `elem`
+ * bytes whose planes lie count bytes apart from d_planes, merged to d_dst -- ElementGather, or with d_base (count x elem bytes)
+ * ElementGatherDelta; *ms = milliseconds a launch, HIP events around `reps` launches after a warming one.  Everything on
+ * `device`.  A measuring hook (tools/dev/delta_bench.py), not a data path. */
+int orz_element_gather_time(int device, const void* d_planes, const void* d_base, void* d_dst, size_t count, uint32_t elem, int reps,
+                            double* ms);
 int orz_reader_tensor_info(orz_reader*, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap);
 int orz_reader_read_elements(orz_reader*, const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges,
                              uint8_t* d_dst, size_t d_cap, uint64_t* dst_len, orz_read_stats* stats);

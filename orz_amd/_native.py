@@ -320,6 +320,12 @@ SYMBOLS = [
     ("orz_reader_cache_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CacheStats)]),
     ("orz_reader_set_planes", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
     ("orz_reader_set_planes_pieces", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
+    ("orz_reader_set_bases", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]),
+    (
+        "orz_element_gather_time",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_double)],
+    ),
     (
         "orz_reader_tensor_info",
         ctypes.c_int,

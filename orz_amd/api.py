@@ -112,6 +112,19 @@ def _base_list(bases, tensors, dev, on_dev, what):
     return bases
 
 
+class _Declared:
+    """a tensor a reader has declared, as far as _base_list asks a tensor: its number of elements and their size"""
+
+    def __init__(self, count, size):
+        self._count, self._size = count, size
+
+    def numel(self):
+        return self._count
+
+    def element_size(self):
+        return self._size
+
+
 def crc32_buffers(tensors, device=0):
     """[zlib.crc32 of each tensor's bytes] (orz_crc32_buffers): contiguous tensors of any dtype, all on cuda:`device` -- digested
     there, where they lie, in three launches and two host waits however many they are -- or all on the CPU."""
@@ -676,8 +689,9 @@ class MemberEncoder:
         says which tensors are deltas, or of what: that travels beside it, like elems and pieces.  digests=True: the tuple gains
         [CRC-32 of each INPUT tensor's bytes], not of the deltas: decode_planes_into(bases=, digests=) holds the restored tensors
         to them, so a delta applied to another base raises OrzDigestError.
-        MemberReader knows nothing of bases: on this container read_elements / read_tensor return the DELTA's elements, the caller
-        XORs the same slice of the base, and read_tensor(..., digest=) of a tensor that has a base raises."""
+        MemberReader(..., bases=) reads element ranges of this container RESTORED, the XOR made in the read's own launch; a reader
+        that has not been told the bases returns the DELTA's elements, and its read_tensor(..., digest=) of a tensor that has a
+        base raises."""
         checked = self._checked_tensors(tensors)
         dev, tensors, on_dev, lengths = checked
         elems = _plane_elems(tensors)
@@ -892,14 +906,19 @@ class MemberReader:
     device, and decode each plane only as far as the furthest element asked of its tensor.
     `pieces`: beside `elems`, what MemberEncoder.encode_tensor_pieces returned: the tensors' planes are cut into pieces, and a
     read decodes only the pieces its ranges touch, side by side.
-    DELTAS (MemberEncoder.encode_tensor_deltas) are beyond the reader: it knows no bases.  On such a container read_elements /
-    read_tensor return the DELTA's elements -- the caller XORs the same slice of the base -- and read_tensor(..., digest=) of a
-    tensor that has a base raises OrzDigestError, since the digest is the tensor's, not the delta's."""
+    `bases`: beside `elems`, the container holds DELTAS (MemberEncoder.encode_tensor_deltas): one entry per tensor, None or the
+    base that tensor was encoded against (see set_bases).  read_elements / read_tensor then return RESTORED elements, planes XOR
+    base, the XOR made in the launch that ends the read: no temporary, the same launches and host waits as without bases, and
+    read_tensor(j, digest=) holds the restored tensor to its digest.  A reader of such a container that has not been told the
+    bases returns the DELTA's elements, and its read_tensor(..., digest=) of a tensor that has a base raises OrzDigestError,
+    since the digest is the tensor's, not the delta's."""
 
-    def __init__(self, src, device=0, members=None, cache_bytes=0, elems=None, pieces=None):
+    def __init__(self, src, device=0, members=None, cache_bytes=0, elems=None, pieces=None, bases=None):
         import torch
 
         self._h = None
+        if bases is not None and elems is None:
+            raise ValueError("bases are those of declared tensors: give elems")
         self._lib = _native.load()
         self._dev = torch.device("cuda", int(device))
         keep, on_dev, ptr, n = _container(src, self._dev)
@@ -914,14 +933,17 @@ class MemberReader:
         self.members, self.total = m.value, tot.value
         self._offsets = None
         self._tensors = []
-        if cache_bytes:
-            self.set_cache(cache_bytes)
-        if elems is not None:
-            try:
+        self._bases = None
+        try:
+            if cache_bytes:
+                self.set_cache(cache_bytes)
+            if elems is not None:
                 self.set_planes(elems, pieces)
-            except Exception:
-                self.close()
-                raise
+            if bases is not None:
+                self.set_bases(bases)
+        except Exception:
+            self.close()
+            raise
 
     @staticmethod
     def cursor_state_bytes():
@@ -993,7 +1015,8 @@ class MemberReader:
         encode_tensor_pieces returns beside them, tensor j is the next elems[j] x pieces[j] members, pieces[j] to a plane
         (orz_reader_set_planes_pieces).  Raises OrzError, with nothing changed, for an element size other than 1, 2, 4, 8, planes
         that are not as many as the members, planes of one tensor that differ in size, or pieces that do not fit together.
-        Cursors are kept and read_ranges does what it did."""
+        Cursors are kept and read_ranges does what it did.  A declaration that succeeds withdraws the bases (set_bases), as the
+        library does: they were those of the tensors declared before."""
         if not self._h:
             raise OrzError("the reader is closed")
         elems = [] if elems is None else [int(e) for e in elems]
@@ -1014,6 +1037,23 @@ class MemberReader:
         sizes = (ctypes.c_uint32 * max(nt, 1))()
         _check(self._lib.orz_reader_tensor_info(self._h, ctypes.byref(n), counts, sizes, nt), "orz_reader_tensor_info")
         self._tensors = [(counts[j], sizes[j]) for j in range(min(n.value, nt))]
+        self._bases = None
+
+    def set_bases(self, bases):
+        """the container holds DELTAS (orz_reader_set_bases): `bases` has one entry per declared tensor, None or the base the tensor
+        was encoded against -- a contiguous tensor on the reader's device with the tensor's element size and number of elements;
+        anything else raises ValueError.  read_elements / read_tensor then return planes XOR base for the tensors that have one.
+        None or an empty list withdraws the bases.  The reader keeps references to the bases while they are set and only reads
+        them.  Nothing is launched and cursors are kept: the same range read against another base decodes nothing anew."""
+        if not self._h:
+            raise OrzError("the reader is closed")
+        bases = [] if bases is None else list(bases)
+        if bases:
+            bases = _base_list(bases, [_Declared(c, e) for c, e in self._tensors], self._dev, self._dev.type == "cuda", "tensors")
+        nb = len(bases)
+        bs = (ctypes.c_void_p * max(nb, 1))(*[(b.data_ptr() if b is not None and b.numel() else None) for b in bases])
+        _check(self._lib.orz_reader_set_bases(self._h, bs, nb), "orz_reader_set_bases")
+        self._bases = bases or None
 
     @property
     def tensors(self):
@@ -1023,7 +1063,9 @@ class MemberReader:
     def read_elements(self, ranges, out=None, stats=False):
         """the elements of [(tensor, first, count), ...], their interleaved bytes back to back in that order, as a uint8 tensor on
         the device (the first bytes of `out` when given: nothing else of it is written)[, stats dict].  Unverified: a part of a
-        tensor has no digest -- read_tensor(j, digest=...) checks a whole one."""
+        tensor has no digest -- read_tensor(j, digest=...) checks a whole one.  With bases set, the ranges of tensors that have a
+        base come back restored; such a range's slice of its base must lie apart from the bytes of `out` that are written, or be
+        exactly where the range's own bytes go (in place), else OrzError naming the range."""
         import torch
 
         if not self._h:
@@ -1064,7 +1106,8 @@ class MemberReader:
         `out`, a contiguous tensor on the device whose element size is the tensor's, the elements are written into it and the
         written slice is returned; otherwise the bytes, viewed as `dtype` when given.  `digest`: the CRC-32 of the WHOLE tensor's
         bytes -- only with first == 0 and count None or all of it, else ValueError: after the read the result is digested on the
-        GPU (crc32_buffers) and OrzDigestError raised when it differs."""
+        GPU (crc32_buffers) and OrzDigestError raised when it differs.  With bases set the elements are the restored ones, and
+        `out=B[first:first + count]`, B being tensor j's base, restores those elements IN PLACE."""
         import torch
 
         j, first = int(j), int(first)
@@ -1101,6 +1144,7 @@ class MemberReader:
             self._lib.orz_reader_close(self._h)
             self._h = None
             self._keep = None
+            self._bases = None
 
     def __del__(self):
         try:

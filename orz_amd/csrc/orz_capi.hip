@@ -1294,6 +1294,49 @@ int plane_move_time(int device, void* d_inter, const void* d_base, void* d_plane
 }
 }  // namespace
 
+// ONE whole-tensor element read's gather alone, timed: `count` elements (a multiple of 16) of `elem` bytes whose planes lie `count`
+// bytes apart from d_planes, merged to d_dst; d_base == nullptr: ElementGather, else ElementGatherDelta with that base
+int orz_element_gather_time(int device, const void* d_planes, const void* d_base, void* d_dst, size_t count, uint32_t elem, int reps, double* ms) {
+    if (!d_planes || !d_dst || !count || count % orz::kPlaneUnit || !ms || reps < 1 || !orz::plane_elem_ok(elem)) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    try {
+        orz::HipBackend be(device);
+        orz::DeviceBuffers<orz::HipBackend> own(be);
+        // ufirst | first | count | member | dst_off | bslice | place[elem] | elem, status[elem] (u32)
+        const uint64_t units = orz::ElementGather::units_of(0, count);
+        std::vector<uint64_t> image(6 + elem + 1 + (elem + 1) / 2, 0);
+        image[2] = count;
+        image[5] = (uint64_t)(uintptr_t)d_base;
+        for (uint32_t p = 0; p < elem; p++) image[6 + p] = (uint64_t)p * count;
+        uint32_t* tail = (uint32_t*)(image.data() + 6 + elem);
+        tail[0] = elem;
+        for (uint32_t p = 0; p < elem; p++) tail[2 + p] = orz::kDecOk;
+        uint64_t* d = own.alloc<uint64_t>(image.size(), false);
+        be.h2d(d, image.data(), image.size() * 8);
+        const uint32_t* d_tail = (const uint32_t*)(d + 6 + elem);
+        const orz::ElementGather g{d, d + 1, d + 2, d + 3, d + 4, d_tail, 1, units, d + 6, d_tail + 2, (const uint8_t*)d_planes, (uint8_t*)d_dst};
+        ORZ_HIP_CHECK(hipEventCreate(&ev.a));
+        ORZ_HIP_CHECK(hipEventCreate(&ev.b));
+        for (int r = -1; r < reps; r++) {  // (the first launch warms up)
+            if (r == 0) ORZ_HIP_CHECK(hipEventRecord(ev.a, be.stream()));
+            if (d_base) be.launch((size_t)units, orz::ElementGatherDelta{g, d + 5});
+            else be.launch((size_t)units, g);
+        }
+        ORZ_HIP_CHECK(hipEventRecord(ev.b, be.stream()));
+        ORZ_HIP_CHECK(hipEventSynchronize(ev.b));
+        float total = 0;
+        ORZ_HIP_CHECK(hipEventElapsedTime(&total, ev.a, ev.b));
+        *ms = (double)total / reps;
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENODEV, e.what());
+    }
+}
+
 // ------------------------------------------------------------------------------ byte ranges of a container
 struct orz_reader {
     std::unique_ptr<orz::HipBackend> be;
@@ -1361,6 +1404,12 @@ int orz_reader_set_planes(orz_reader* r, const uint32_t* elems, size_t n_tensors
 int orz_reader_set_planes_pieces(orz_reader* r, const uint32_t* elems, const uint32_t* pieces, size_t n_tensors) {
     if (!r || (n_tensors && !pieces)) return fail(ORZ_EINVAL, "bad argument");
     return mapped([&] { r->el->set_planes(elems, n_tensors, pieces); });
+}
+
+int orz_reader_set_bases(orz_reader* r, const void* const* bases, size_t n_tensors) {
+    static_assert(sizeof(void*) == sizeof(uint64_t), "the bases are handed to the device as 64-bit words");
+    if (!r) return fail(ORZ_EINVAL, "bad argument");
+    return mapped([&] { r->el->set_bases((const uint64_t*)bases, n_tensors); });
 }
 
 int orz_reader_tensor_info(orz_reader* r, uint64_t* n_tensors, uint64_t* counts, uint32_t* elems, size_t cap) {

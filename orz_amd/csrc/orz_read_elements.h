@@ -128,6 +128,129 @@ struct ElementGatherPieces {
     ORZ_HD void operator()(size_t unit) const { g.gather_unit<true>((uint64_t)unit, psize, pieces); }
 };
 
+// ------------------------------------------------------------------------------------------------ deltas against base tensors
+// ElementGatherDelta / ElementGatherDeltaPieces are ElementGather / ElementGatherPieces with one more column: bslice[k], the
+// address of the BASE's bytes for range k's first element -- base[tensor[k]] + first[k] * elem[k], worked out on the host -- or 0:
+// range k has no base.  The members hold the planes of tensor XOR base (orz_planes.h), and a unit of a range with a base writes
+// planes XOR base, its base bytes at bslice[k] + (lo - first[k]) e: the gather loads every plane byte and stores every output byte
+// once anyway, so that is where the base comes in, as PlaneMergeDelta took it into the merge.  Work units, the search over the
+// ranges, the piece arithmetic and the status check are ElementGather's.  A full unit over planes at multiples of 16 whose
+// destination and base address are multiples of 4: the e 16-byte plane loads and the 16 e base bytes -- 16 at a time where the
+// base address is a multiple of 16, dwords otherwise -- ALL issued before the first store, the XOR on the 4 e interleaved dwords
+// behind the shuffle, and the stores of element_unit_merge.  Every other unit goes byte by byte, each base byte read just before
+// the byte at the same index is written.  A range without a base moves exactly as ElementGather moves it; a unit with a plane
+// whose decode failed writes nothing.  No LDS, no scratch, no atomics, and the rule of DESIGN 2a: a lane reads and writes its own
+// unit only -- which makes a read IN PLACE safe, bslice[k] == the range's destination: the lane has loaded its base bytes before
+// it stores over them, and no other lane reads them.
+// The bodies are their own, not gather_unit with a parameter more: the plain kernels keep their code and registers.
+
+// a dword of device memory at a multiple of 4, loaded from the GLOBAL address space (as plane_load16 loads sixteen bytes)
+ORZ_HD uint32_t element_load4(const uint8_t* s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(__attribute__((address_space(1))) const uint32_t*)s;
+#else
+    uint32_t v;
+    __builtin_memcpy(&v, s, 4);
+    return v;
+#endif
+}
+
+// element_unit_merge with a base: the 16 E base bytes at bs, a multiple of 4, XORed into the interleaved dwords
+template <int E>
+ORZ_HD void element_unit_merge_delta(uint8_t* d, const uint8_t* bs, uint64_t base, const uint64_t* place, uint64_t lo, uint64_t Q) {
+    uint32_t w[4 * E], x[4 * E], pl[4 * E];
+#pragma unroll
+    for (int p = 0; p < E; p++) plane_load16(pl + 4 * p, (const uint8_t*)(uintptr_t)(base + place[(uint64_t)p * Q] + lo));
+    if (((uintptr_t)bs & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_load16(x + 4 * q, bs + 16 * q);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4 * E; q++) x[q] = element_load4(bs + 4 * q);
+    }
+    if constexpr (E == 1) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) w[q] = pl[q];
+    } else {
+        plane_merge_shuffle<E>(pl, w);
+    }
+#pragma unroll
+    for (int q = 0; q < 4 * E; q++) w[q] ^= x[q];
+    if (((uintptr_t)d & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < E; q++) plane_store16(d + 16 * q, w + 4 * q);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4 * E; q++) element_store4(d + 4 * q, w[q]);
+    }
+}
+
+struct ElementGatherDelta {
+    ElementGather g;
+    const uint64_t* bslice;  // [n_ranges] where the base's bytes for the range's first element lie (0: no base)
+    ORZ_HD void operator()(size_t unit) const { gather_unit<false>((uint64_t)unit, nullptr, nullptr); }
+    // unit u; kPieces, psize, pieces as ElementGather::gather_unit takes them
+    template <bool kPieces>
+    ORZ_HD void gather_unit(uint64_t u, const uint64_t* psize, const uint64_t* pieces) const {
+        if (u >= g.units || !g.n_ranges) return;
+        const uint64_t k = last_at_or_below(g.ufirst, g.n_ranges, u);
+        const uint64_t f = g.first[k], end = f + g.count[k];
+        const uint64_t block = (f / kPlaneUnit + (u - g.ufirst[k])) * kPlaneUnit;
+        const uint64_t lo = block > f ? block : f, hi = block + kPlaneUnit < end ? block + kPlaneUnit : end;
+        if (lo >= hi) return;
+        const uint32_t e = g.elem[k];
+        const uint64_t Q = kPieces ? pieces[k] : 1, q = kPieces ? block / psize[k] : 0;
+        const uint64_t in = lo - (kPieces ? q * psize[k] : 0);
+        const uint64_t* pl = g.place + g.member[k] + q;
+        const uint32_t* st = g.status + g.member[k] + q;
+        const uint64_t b = (uint64_t)(uintptr_t)g.base;
+        uint64_t bits = 0;
+        for (uint32_t p = 0; p < e; p++) {
+            if (st[(uint64_t)p * Q] != kDecOk) return;
+            bits |= b + pl[(uint64_t)p * Q] + in;
+        }
+        uint8_t* const d = g.dst + g.dst_off[k] + (lo - f) * e;
+        const bool quads = hi - lo == kPlaneUnit && (bits & 15) == 0 && ((uintptr_t)d & 3) == 0 && (e == 1 || e == 2 || e == 4 || e == 8);
+        const uint32_t n = (uint32_t)(hi - lo);
+        const uint64_t b0 = bslice[k];
+        if (!b0) {  // no base: as ElementGather moves it
+            if (quads) {
+                if (e == 1) element_unit_merge<1>(d, b, pl, in, Q);
+                else if (e == 2) element_unit_merge<2>(d, b, pl, in, Q);
+                else if (e == 4) element_unit_merge<4>(d, b, pl, in, Q);
+                else element_unit_merge<8>(d, b, pl, in, Q);
+                return;
+            }
+            for (uint32_t p = 0; p < e; p++) {
+                const uint8_t* s = (const uint8_t*)(uintptr_t)(b + pl[(uint64_t)p * Q] + in);
+                for (uint32_t i = 0; i < n; i++) d[(uint64_t)i * e + p] = s[i];
+            }
+            return;
+        }
+        const uint8_t* const bs = (const uint8_t*)(uintptr_t)b0 + (lo - f) * e;
+        if (quads && ((uintptr_t)bs & 3) == 0) {
+            if (e == 1) element_unit_merge_delta<1>(d, bs, b, pl, in, Q);
+            else if (e == 2) element_unit_merge_delta<2>(d, bs, b, pl, in, Q);
+            else if (e == 4) element_unit_merge_delta<4>(d, bs, b, pl, in, Q);
+            else element_unit_merge_delta<8>(d, bs, b, pl, in, Q);
+            return;
+        }
+        for (uint32_t p = 0; p < e; p++) {
+            const uint8_t* s = (const uint8_t*)(uintptr_t)(b + pl[(uint64_t)p * Q] + in);
+            for (uint32_t i = 0; i < n; i++) {  // (in place the base byte IS the byte written: read first)
+                const uint64_t a = (uint64_t)i * e + p;
+                d[a] = (uint8_t)(s[i] ^ bs[a]);
+            }
+        }
+    }
+};
+
+struct ElementGatherDeltaPieces {
+    ElementGatherDelta g;
+    const uint64_t *psize, *pieces;  // [n_ranges], as ElementGatherPieces'
+    ORZ_HD void operator()(size_t unit) const { g.gather_unit<true>((uint64_t)unit, psize, pieces); }
+};
+
 // The declaration of a reader's container as plane-encoded tensors, and the reads of element ranges it allows.  It borrows the
 // reader (declared before it, destroyed after it) and keeps nothing on the device of its own.
 template <class BE>
@@ -139,6 +262,7 @@ struct ElementReader {
     std::vector<uint64_t> pieces;   // [tensors] pieces to a plane
     std::vector<uint64_t> psize;    // [tensors] elements to a piece (of one piece: the tensor's count, or 1 when it has none)
     bool pieced = false;            // some tensor has more than one piece to a plane
+    std::vector<uint64_t> bases;    // [tensors] the address of a tensor's base (0: none); empty = no bases (set_bases)
     explicit ElementReader(RangeReader<BE>& r) : rd(r) {}
 
     // Tensor j is the next e[j] members, plane 0 first -- with `q`, the next e[j] x q[j] members, q[j] pieces to a plane,
@@ -178,10 +302,45 @@ struct ElementReader {
         pieces.swap(pcs);
         psize.swap(psz);
         pieced = cut;
+        bases.clear();  // (they were those of the tensors declared before)
+    }
+
+    // DELTAS: the members hold the planes of tensor XOR base (orz_members_encode_deltas_to_device), and b[j] is the address of
+    // tensor j's base -- counts[j] x elems[j] bytes of device memory on the reader's device -- or 0 for none; reads then return
+    // planes XOR base.  n must be the number of tensors declared; n == 0 withdraws the bases, as every successful set_planes
+    // does (a refused one leaves them).  The bases are borrowed and only read: one may overlap the container or another base.  A
+    // base of a tensor of no elements is not looked at.  Throws RangeArgumentError with nothing changed.  Launches nothing and
+    // waits for nothing; cursors are kept: they hold planes and know nothing of bases.
+    void set_bases(const uint64_t* b, size_t n) {
+        if (n == 0) {
+            bases.clear();
+            return;
+        }
+        if (elems.empty()) throw RangeArgumentError("invalid argument: the container is not declared as planes of tensors");
+        if (n != elems.size())
+            throw RangeArgumentError("invalid argument: " + std::to_string(n) + " bases for " + std::to_string(elems.size()) + " tensors");
+        if (!b) throw RangeArgumentError("invalid argument: bases without their array");
+        std::vector<uint64_t> bs(n, 0);
+        for (size_t j = 0; j < n; j++) {
+            const uint64_t len = counts[j] * elems[j];  // (a plane holds less than 2^32 bytes a piece: no overflow)
+            if (!len || !b[j]) continue;
+            if (len > (uint64_t)0 - b[j])
+                throw RangeArgumentError("invalid argument: the base of tensor " + std::to_string(j) + " (" + std::to_string(len) +
+                                         " bytes) wraps the address space");
+            bs[j] = b[j];
+        }
+        bases.swap(bs);
     }
 
     // Elements [first[k], first[k] + count[k]) of tensor tensor[k], their interleaved bytes back to back in range order at d_dst.
     // dst_len = the sum of the bytes whenever the ranges are valid.  Throws what RangeReader::read throws, for the same reasons.
+    // With bases (set_bases): when a range that has elements names a tensor with a base, the ranges' base slices go up as one more
+    // column of the read's ONE upload and ElementGatherDelta(Pieces) ends the read where the plain gather would, so the ranges of
+    // tensors with a base come back as planes XOR base in the same launches and host waits; otherwise the read is the one without
+    // bases, kernel and upload.  The base slice of such a range -- its count x e bytes from base + first x e -- must be disjoint
+    // from ALL the bytes the read writes, [d_dst, d_dst + dst_len), or begin exactly where the range's own bytes go: the read IN
+    // PLACE, after which the slice holds the restored elements.  Any other overlap would be overwritten by, or overwrite, another
+    // range: RangeArgumentError naming the range, before anything reaches the device.
     void read(const uint64_t* tensor, const uint64_t* first, const uint64_t* count, size_t n_ranges, uint8_t* d_dst, size_t d_cap,
               uint64_t& dst_len, RangeReadStats& st, uint32_t slots = 2048) {
         BE& be = rd.be;
@@ -194,6 +353,7 @@ struct ElementReader {
         const size_t K = n_ranges, T = elems.size();
         size_t B = 0;  // byte ranges: one per plane, and per piece touched, of every element range
         uint64_t sum = 0;
+        bool delta = false;  // a range that has elements names a tensor with a base
         for (size_t k = 0; k < K; k++) {
             if (tensor[k] >= T)
                 throw RangeArgumentError("invalid argument: range " + std::to_string(k) + " names tensor " + std::to_string(tensor[k]) + " of " +
@@ -207,12 +367,13 @@ struct ElementReader {
             const uint64_t bytes = count[k] * elems[j];
             if (sum + bytes < sum) throw RangeArgumentError("invalid argument: the ranges' lengths overflow 64 bits");
             sum += bytes;
+            delta = delta || (bytes && !bases.empty() && bases[j]);
             if (!pieced) B += elems[j];
             else if (count[k]) B += elems[j] * (size_t)((first[k] + count[k] - 1) / psize[j] - first[k] / psize[j] + 1);  // (an empty range: none)
         }
         // off | len | prefix of the byte ranges, as RangeReader::run takes them; behind them the element ranges' columns (with
-        // pieces: psize and pieces too)
-        const size_t x = 3 * B + 1, C = pieced ? 7 : 5;
+        // pieces: psize and pieces too; of a delta read: bslice last)
+        const size_t x = 3 * B + 1, C = (pieced ? 7 : 5) + (delta ? 1 : 0);
         std::vector<uint64_t> up(x + C * K + (K + 1) / 2, 0);
         uint32_t* u_elem = (uint32_t*)(up.data() + x + C * K);
         const std::vector<uint64_t>& m_off = rd.member_offsets();  // (fetched by set_planes: no wait)
@@ -227,6 +388,7 @@ struct ElementReader {
             up[x + 3 * K + k] = first_m[j];
             up[x + 4 * K + k] = at;
             u_elem[k] = e;
+            if (delta && count[k] && bases[j]) up[x + (C - 1) * K + k] = bases[j] + first[k] * e;
             units += ElementGather::units_of(first[k], count[k]);
             if (!pieced) {
                 for (uint32_t p = 0; p < e; p++, b++) {
@@ -258,10 +420,21 @@ struct ElementReader {
             st.total_s = be.now() - t0;
             return;
         }
+        if (delta) {
+            const uint64_t d0 = (uint64_t)(uintptr_t)d_dst;
+            for (size_t k = 0; k < K; k++) {
+                const uint64_t s = up[x + (C - 1) * K + k], n = count[k] * elems[tensor[k]];
+                if (!s || s + n <= d0 || s >= d0 + sum || s == d0 + up[x + 4 * K + k]) continue;
+                throw RangeArgumentError("invalid argument: the base slice of range " + std::to_string(k) + " (tensor " + std::to_string(tensor[k]) +
+                                         ") overlaps the output buffer other than as the range's own destination");
+            }
+        }
         rd.run(up, B, st, slots, t0, [&](const uint64_t* d_up, const uint64_t* d_place, const uint8_t* base) {
             const uint64_t* c = d_up + x;
             const ElementGather g{c, c + K, c + 2 * K, c + 3 * K, c + 4 * K, (const uint32_t*)(c + C * K), K, units, d_place, rd.status(), base, d_dst};
-            if (pieced) be.launch((size_t)units, ElementGatherPieces{g, c + 5 * K, c + 6 * K});
+            if (delta && pieced) be.launch((size_t)units, ElementGatherDeltaPieces{ElementGatherDelta{g, c + 7 * K}, c + 5 * K, c + 6 * K});
+            else if (delta) be.launch((size_t)units, ElementGatherDelta{g, c + 5 * K});
+            else if (pieced) be.launch((size_t)units, ElementGatherPieces{g, c + 5 * K, c + 6 * K});
             else be.launch((size_t)units, g);
         });
     }

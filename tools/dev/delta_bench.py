@@ -1,5 +1,6 @@
-"""dev: what the delta layout costs and buys (orz_planes.h: PlaneSplitDelta / PlaneMergeDelta).  Five legs, each once, in a child
-process of its own under its own time limit, one JSON line per leg into --out (default profiles/delta_bench.jsonl):
+"""dev: what the delta layout costs and buys (orz_planes.h: PlaneSplitDelta / PlaneMergeDelta; orz_read_elements.h:
+ElementGatherDelta).  Nine legs, each once, in a child process of its own under its own time limit, one JSON line per leg into
+--out (default profiles/delta_bench.jsonl; --only PREFIX runs the legs whose names begin with it and APPENDS their lines):
 
   kernels, e = 1 / 2 / 4 / 8   PlaneSplitDelta and PlaneMergeDelta over ONE tensor of 256 MiB and its base, all at 16-aligned
                                addresses (orz_plane_delta_move_time: events around 5 launches after a warming one); beside them, in
@@ -10,7 +11,11 @@ process of its own under its own time limit, one JSON line per leg into --out (d
   bf16 16 Mi, plain and delta  w = randn * 0.02 and its successor w + randn * 1e-4, 16 Mi bf16 elements, as pieces of 2^18:
                                the successor through encode_tensor_pieces / decode_planes_into and through encode_tensor_deltas /
                                decode_planes_into(bases=) in ONE process -- container bytes, encode wall time (median of 3 after a
-                               warm-up) and the decode's kernel_ms, the delta's each against the plain one's."""
+                               warm-up) and the decode's kernel_ms, the delta's each against the plain one's.
+  gather, e = 1 / 2 / 4 / 8    the launch that ends ONE whole-tensor element read of a 256 MiB tensor (orz_element_gather_time: events
+                               around 5 launches after a warming one): ElementGatherDelta against ElementGather over the same planes,
+                               all at 16-aligned addresses.  Three bytes carried where the plain gather carries two: about 1.5 x
+                               is what bandwidth predicts.  Both results, and the gather in place, are checked."""
 import argparse
 import ctypes
 import json
@@ -24,7 +29,8 @@ sys.path.insert(0, os.getcwd())
 
 KERNEL_BYTES, REPS = 256 << 20, 5
 ELEMENTS, PIECE, JOBS, LR = 16 << 20, 1 << 18, 4, 1e-4
-LEGS = ["kernels, e = 1", "kernels, e = 2", "kernels, e = 4", "kernels, e = 8", "bf16 16 Mi, plain and delta"]
+LEGS = ["kernels, e = 1", "kernels, e = 2", "kernels, e = 4", "kernels, e = 8", "bf16 16 Mi, plain and delta", "gather, e = 1", "gather, e = 2",
+        "gather, e = 4", "gather, e = 8"]
 LIMIT_S = 240
 
 
@@ -89,6 +95,44 @@ def kernels(e):
     return r
 
 
+def gather(e):
+    import torch
+
+    from orz_amd import _native
+
+    lib = _native.load()
+    count = KERNEL_BYTES // e
+    g = torch.Generator(device="cuda:0").manual_seed(10 + e)
+    planes = torch.randint(0, 256, (KERNEL_BYTES,), generator=g, dtype=torch.uint8, device="cuda:0")  # plane p: bytes [p count, (p + 1) count)
+    base = torch.randint(0, 256, (KERNEL_BYTES,), generator=g, dtype=torch.uint8, device="cuda:0")
+    out = torch.empty(KERNEL_BYTES, dtype=torch.uint8, device="cuda:0")
+    assert count % 16 == 0 and all(t.data_ptr() % 16 == 0 for t in (planes, base, out))
+    torch.cuda.synchronize()
+    ms = ctypes.c_double()
+
+    def run(b, dst, reps=REPS):
+        rc = lib.orz_element_gather_time(0, ctypes.c_void_p(planes.data_ptr()), ctypes.c_void_p(b.data_ptr()) if b is not None else None,
+                                         ctypes.c_void_p(dst.data_ptr()), count, e, reps, ctypes.byref(ms))
+        assert rc == 0, _native.last_error()
+        return ms.value
+
+    merged = planes.view(e, count).t().contiguous().view(-1)  # the interleaved bytes, in torch
+    r = {"bytes": KERNEL_BYTES, "elem": e}
+    r["gather_ms"] = round(run(None, out), 4)
+    exact = bool(torch.equal(out, merged))
+    r["gather_delta_ms"] = round(run(base, out), 4)
+    exact = exact and bool(torch.equal(out, merged ^ base))
+    # in place, checked and not timed: out := base, gathered over itself.  The hook launches twice (the warming launch and one rep):
+    # the first leaves planes XOR base, the second XORs the planes in again and leaves the base
+    out.copy_(base)
+    torch.cuda.synchronize()
+    run(out, out, reps=1)
+    r["in_place_twice_is_the_base"] = bool(torch.equal(out, base))
+    r.update(exact=exact, delta_over_plain=round(r["gather_delta_ms"] / r["gather_ms"], 3),
+             gather_GBps_of_tensor=round(KERNEL_BYTES / r["gather_ms"] / 1e6, 1), gather_delta_GBps_of_tensor=round(KERNEL_BYTES / r["gather_delta_ms"] / 1e6, 1))
+    return r
+
+
 def step():
     import torch
 
@@ -131,7 +175,8 @@ def run_leg(leg):
     import torch
 
     r = {"leg": leg}
-    r.update(kernels(int(leg.rsplit(" ", 1)[1])) if leg.startswith("kernels") else step())
+    e = int(leg.rsplit(" ", 1)[1]) if " e = " in leg else 0
+    r.update(kernels(e) if leg.startswith("kernels") else gather(e) if leg.startswith("gather") else step())
     r["device"] = torch.cuda.get_device_name(0)
     print("ROW " + json.dumps(r), flush=True)
 
@@ -140,12 +185,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "delta_bench.jsonl"))
     ap.add_argument("--leg", default="")
+    ap.add_argument("--only", default="", help="run the legs whose names begin with this, and append their lines to --out")
     args = ap.parse_args()
     if args.leg:
         run_leg(args.leg)
         return
     rows = []
-    for leg in LEGS:
+    if args.only and os.path.exists(args.out):
+        rows = [json.loads(ln) for ln in open(args.out) if ln.strip()]
+    for leg in [x for x in LEGS if x.startswith(args.only)]:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg], stdout=subprocess.PIPE, text=True, timeout=LIMIT_S)
         if p.returncode != 0:  # (whatever failed on the device: nothing more is started on it)
             sys.exit("leg %r failed with status %d" % (leg, p.returncode))
