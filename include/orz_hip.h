@@ -493,6 +493,45 @@ int orz_decode_tensors_delta(int device, const void* src, size_t n, int src_on_d
 uint64_t orz_decode_tensors_delta_host_waits(void);
 int orz_plane_delta_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge,
                               int reps, double* ms);
+/* CHAINS: deltas are kept as a chain -- a keyframe every N steps and a delta per step against the step before.  A chain container
+ * is `links` LINKS one behind the other, each byte for byte a container orz_members_encode_planes_pieces_to_device or
+ * orz_members_encode_deltas_to_device wrote for the same list of tensors: the same element sizes and the same piece_elems, so the
+ * same elems, pieces and number of members M1 = sum(elems[j] x pieces[j]).  The container has links x M1 members, link-major,
+ * found from the framing or from a member table as in every other call.  Nothing in the format says so: that a container is a
+ * chain travels beside it as elems, pieces, bases and digests do.  XOR is associative and commutes with the split into planes
+ * and pieces, so
+ *     destination j = d_bases[j] XOR (tensor j of link 0) XOR ... XOR (tensor j of link `links` - 1)
+ *   is made in the plane domain in ONE merge launch (PlaneMergeChain) behind ONE decode of all links' members, which decode side
+ *   by side in the same rounds.  THE ORDER OF THE LINKS DOES NOT MATTER to the result.  Without a base the result is the XOR of
+ *   the links: a chain whose link 0 is a plain keyframe restores without bases, and a chain of deltas alone yields the composed
+ *   delta, which a caller can encode again to shorten a chain.
+ * orz_decode_tensors_chain: the arguments and the contract of orz_decode_tensors_delta, with `links` and these differences.
+ *   d_bases may be NULL: no bases at all.  links == 1 IS orz_decode_tensors_delta (without d_bases: orz_decode_tensors_verified,
+ *   or orz_decode_members_planes_pieces without crcs) -- the same launches, uploads, host waits and messages.  For any `links`
+ *   the host waits are those of orz_decode_members_planes_pieces for the same container -- 4, +1 for a member table, +1 for a
+ *   host container, +1 with crcs -- and the launches those of orz_decode_tensors_delta for a container of as many members.  crcs
+ *   are the digests of the FINAL tensors: nobody needs the digests of the steps in between, and a destination restored in place
+ *   never holds one of them.  out_lens are link 0's sizes.  Every destination is staged, single bytes too: staging memory, freed
+ *   before the call returns, is `links` times the tensors' bytes (and 32 bytes a member).
+ *   ORZ_EINVAL before any decode launch, with nothing written anywhere, each naming what offends: links == 0 (before anything
+ *   reaches a device); links x M1 different from the member count ("K links of M1 members for M members"); per link what
+ *   orz_decode_members_planes_pieces refuses of pieces and planes, naming the link and the member; a tensor whose planes in link k
+ *   have another size than in link 0, naming k, the destination and both sizes; everything orz_decode_tensors_delta refuses of
+ *   destinations and bases.  ORZ_ENOMEM: a short destination, as there; staging memory that cannot be had.
+ *   AFTER A FAILURE behind the launches -- payload damage (ORZ_EINVAL naming the member) or a digest mismatch -- a base given out
+ *   of place is untouched, and a destination restored in place holds NEITHER its base NOR its tensor.
+ *   A reader (orz_reader_*) on a chain container still sees single links: it knows nothing of chains.
+ * orz_decode_tensors_chain_host_waits: the host waits of the calling thread's last such call.
+ * orz_plane_chain_move_time: orz_plane_delta_move_time for PlaneMergeChain: `links` plane sets, link k's planes
+ *   elem x (count rounded up to 16) bytes behind link k - 1's, from d_planes; d_base may be NULL (no base).  A measuring hook
+ *   (tools/dev/chain_bench.py), not a data path. */
+int orz_decode_tensors_chain(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens,
+                             size_t n_members, uint8_t* const* d_dsts, const size_t* d_caps, const void* const* d_bases,
+                             const uint32_t* elems, const uint32_t* pieces, size_t n_dsts, const uint32_t* crcs, uint32_t links,
+                             size_t* out_lens, uint32_t* out_crcs, size_t* n_members_out, orz_decode_stats* stats);
+uint64_t orz_decode_tensors_chain_host_waits(void);
+int orz_plane_chain_move_time(int device, void* d_inter, const void* d_base, const void* d_planes, size_t count, uint32_t elem,
+                              uint32_t links, int reps, double* ms);
 
 /* ---- byte ranges of a members container (orz_decode_range.h) ------------------------------------------
  * A reader indexes a container ONCE (on the device, as orz_decode_members_to_device does) and then serves reads of byte

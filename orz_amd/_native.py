@@ -269,6 +269,21 @@ SYMBOLS = [
         [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
          ctypes.POINTER(ctypes.c_double)],
     ),
+    (
+        "orz_decode_tensors_chain",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+         ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+         ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(DecodeStats)],
+    ),
+    ("orz_decode_tensors_chain_host_waits", ctypes.c_uint64, []),
+    (
+        "orz_plane_chain_move_time",
+        ctypes.c_int,
+        [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+         ctypes.POINTER(ctypes.c_double)],
+    ),
     ("orz_members_new_multi", ctypes.c_void_p, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(LZCfg), ctypes.c_int]),
     ("orz_members_new", ctypes.c_void_p, [ctypes.c_int, ctypes.POINTER(LZCfg), ctypes.c_int]),
     ("orz_members_free", None, [ctypes.c_void_p]),

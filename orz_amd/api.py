@@ -691,7 +691,12 @@ class MemberEncoder:
         to them, so a delta applied to another base raises OrzDigestError.
         MemberReader(..., bases=) reads element ranges of this container RESTORED, the XOR made in the read's own launch; a reader
         that has not been told the bases returns the DELTA's elements, and its read_tensor(..., digest=) of a tensor that has a
-        base raises."""
+        base raises.
+        CHAINS: the deltas of consecutive steps, each against the step before and all with the same piece_elems, are the links of
+        a chain: join_links puts them (and a keyframe, if any) into one container, and decode_planes_into(..., links=K) restores
+        the last step in ONE decode and ONE merge launch, with the host waits of one call and digests of the last step alone.
+        The order of the links does not matter; staging memory is K times the tensors' bytes, freed before the call returns;
+        a reader on a chain container still sees single links."""
         checked = self._checked_tensors(tensors)
         dev, tensors, on_dev, lengths = checked
         elems = _plane_elems(tensors)
@@ -796,10 +801,14 @@ def decode_members_to_device(src, device=0, members=None, out=None, offsets=Fals
     return tuple(res)
 
 
-def _decode_into(planes, src, outs, device, members, elems, pieces, digests, stats, bases=None):
+def _decode_into(planes, src, outs, device, members, elems, pieces, digests, stats, bases=None, links=None):
     """decode_members_into (planes False: member k into outs[k]) and decode_planes_into: their checks in one order, the one ABI
     call that serves the arguments, and that call's own count of host waits"""
     import torch
+
+    if links is not None:
+        if isinstance(links, bool) or not isinstance(links, int) or not 1 <= links < 1 << 32:
+            raise ValueError("links is None or the number of links of a chain, an integer from 1 to 2^32 - 1")
 
     lib = _native.load()
     dev = torch.device("cuda", int(device))
@@ -830,8 +839,13 @@ def _decode_into(planes, src, outs, device, members, elems, pieces, digests, sta
     if digests is not None:
         digests, want = _digest_array(digests, nd)
         got = (ctypes.c_uint32 * max(nd, 1))()
+    bs = None
     if bases is not None:
         bs = (ctypes.c_void_p * max(nd, 1))(*[(b.data_ptr() if b is not None and b.numel() else None) for b in bases])
+    if links is not None:
+        name = "orz_decode_tensors_chain"
+        layout = (bs, el, pc, nd, want if digests is not None else None, links, sizes, got if digests is not None else None)
+    elif bases is not None:
         name, layout = "orz_decode_tensors_delta", (bs, el, pc, nd, want if digests is not None else None, sizes, got if digests is not None else None)
     elif digests is not None:
         name, layout = "orz_decode_tensors_verified", (el, pc, nd, want, sizes, got)
@@ -867,7 +881,7 @@ def decode_members_into(src, outs, device=0, members=None, stats=False, digests=
     return _decode_into(False, src, outs, device, members, None, None, digests, stats)
 
 
-def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None, digests=None, bases=None):
+def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=False, pieces=None, digests=None, bases=None, links=None):
     """decode plane members ON THE GPU and merge them (orz_decode_members_planes): `outs[k]` takes the next elems[k] members as
     the byte planes of its elements -- what MemberEncoder.encode_tensor_planes wrote.  `src` and `members` as for
     decode_members_into; `outs`: contiguous tensors on cuda:`device`, each at least as large as its planes together; `elems`:
@@ -887,8 +901,49 @@ def decode_planes_into(src, outs, device=0, members=None, elems=None, stats=Fals
     another of `outs`, raises OrzError with nothing written.  `digests` are those of the restored tensors, so a wrong base raises
     OrzDigestError.  After payload damage or a digest error a base given out of place is untouched; a tensor restored in place
     holds neither its base nor the tensor.  The default, None, changes nothing: the same call and the same waits as before.
+    `links`: the container is a CHAIN of that many links (join_links), each what encode_tensor_pieces or encode_tensor_deltas
+    wrote for the same list of tensors with the same piece size -- a keyframe and the deltas of the steps behind it, or deltas
+    alone -- and `elems`, `pieces` are those of ONE link.  `outs[k]` gets `bases[k]` (if any) XOR tensor k of every link
+    (orz_decode_tensors_chain, with or without `pieces`, `bases`, `digests`, `members` and `stats`): all links' members decode
+    side by side, ONE merge launch XORs them, and the host waits are those of one call whatever the number of links.  The order
+    of the links does not matter to the result.  Without `bases` the result is the XOR of the links: a chain that starts with a
+    plain keyframe restores without one.  `digests` are those of the final tensors.  In place and after a failure as for `bases`.
+    It costs staging memory of `links` times the tensors' bytes, freed before the call returns.  links=1 is the call without
+    `links`; None (the default) changes nothing: the same ABI call and the same host waits as before; anything but None or an
+    integer >= 1 raises ValueError.  A MemberReader on a chain container still sees single links: it knows nothing of chains.
     Returns [decoded size of each tensor] (and the stats dict, with `host_waits`)."""
-    return _decode_into(True, src, outs, device, members, elems, pieces, digests, stats, bases)
+    return _decode_into(True, src, outs, device, members, elems, pieces, digests, stats, bases, links)
+
+
+def join_links(links):
+    """one chain container of the links of a chain: `links` is a list of (container, members) pairs as the encode_tensor_* calls
+    return them -- containers all uint8 tensors on one device, or all bytes-like -- in any order (XOR commutes).  Returns (container,
+    members): the containers one behind the other and ONE member table, link-major, each link's offsets shifted by what lies in
+    front of it -- what decode_planes_into(..., members=, links=len(links)) takes.  Mixed residency or no links raises ValueError."""
+    import torch
+
+    links = [(c, list(m)) for c, m in links]
+    if not links:
+        raise ValueError("a chain has at least one link")
+    tensors = [isinstance(c, torch.Tensor) for c, _ in links]
+    if any(tensors) and not all(tensors):
+        raise ValueError("the containers of a chain are all tensors or all bytes")
+    if tensors[0]:
+        if any(c.dtype != torch.uint8 or c.dim() != 1 for c, _ in links):
+            raise ValueError("a container is a uint8 tensor of one dimension")
+        if any(c.device != links[0][0].device for c, _ in links):
+            raise ValueError("the containers of a chain lie on one device")
+        sizes = [c.numel() for c, _ in links]
+        joined = torch.cat([c for c, _ in links])
+    else:
+        blobs = [bytes(c) for c, _ in links]
+        sizes = [len(b) for b in blobs]
+        joined = b"".join(blobs)
+    table, at = [], 0
+    for (_, members), size in zip(links, sizes):
+        table += [(int(o) + at, int(ln)) for o, ln in members]
+        at += size
+    return joined, table
 
 
 class MemberReader:

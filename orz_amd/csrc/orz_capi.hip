@@ -22,6 +22,7 @@
 #include "orz_decode_scatter.h"
 #include "orz_host_decode.h"
 #include "orz_planes.h"
+#include "orz_chain.h"
 #include "orz_read_elements.h"
 #include "orz_decode_check.h"
 #include "orz_stream.h"
@@ -1242,6 +1243,67 @@ int orz_decode_tensors_delta(int device, const void* src, size_t n, int src_on_d
     });
 }
 uint64_t orz_decode_tensors_delta_host_waits(void) { return g_delta_waits; }
+
+thread_local uint64_t g_chain_waits = 0;
+int orz_decode_tensors_chain(int device, const void* src, size_t n, int src_on_device, const size_t* offs, const size_t* lens, size_t n_members,
+                             uint8_t* const* d_dsts, const size_t* d_caps, const void* const* d_bases, const uint32_t* elems, const uint32_t* pieces,
+                             size_t n_dsts, const uint32_t* crcs, uint32_t links, size_t* out_lens, uint32_t* out_crcs, size_t* n_members_out,
+                             orz_decode_stats* stats) {
+    const bool bad = (!src && n) || (!offs != !lens) || (d_dsts && n_dsts && !d_caps);
+    if (!bad && !links) {
+        g_chain_waits = 0;
+        return fail(ORZ_EINVAL, "invalid argument: a chain of 0 links");
+    }
+    return decode_into_list(g_chain_waits, bad, device, n_members_out, stats, [&](orz::HipBackend& be, uint64_t& members, orz::DecodeScatterStats& st) {
+        const std::vector<uint32_t> ones(elems ? 0 : n_dsts + 1, 1);  // (no element sizes: bytes, a member per destination and link)
+        const orz::CrcCheck check{d_dsts && crcs ? crc_device_image(device) : nullptr, crcs, out_crcs};
+        orz::decode_members_chain(be, (const uint8_t*)src, n, src_on_device != 0, offs != nullptr, (const uint64_t*)offs, (const uint64_t*)lens,
+                                  n_members, d_dsts, (const uint64_t*)d_caps, elems ? elems : ones.data(), n_dsts, (uint64_t*)out_lens, members, st,
+                                  decode_slots(), pieces, crcs ? &check : nullptr, (const uint64_t*)d_bases, links);
+    });
+}
+uint64_t orz_decode_tensors_chain_host_waits(void) { return g_chain_waits; }
+
+// `reps` PlaneMergeChain launches over ONE tensor whose `links` plane sets lie elem x plane_pitch(count) bytes apart from d_planes
+int orz_plane_chain_move_time(int device, void* d_inter, const void* d_base, const void* d_planes, size_t count, uint32_t elem, uint32_t links,
+                              int reps, double* ms) {
+    if (!d_inter || !d_planes || !count || !links || !ms || reps < 1 || !orz::plane_elem_ok(elem)) return fail(ORZ_EINVAL, "bad argument");
+    if (!device_ok(device)) return fail(ORZ_ENODEV, "no such HIP device");
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    try {
+        orz::HipBackend be(device);
+        orz::DeviceBuffers<orz::HipBackend> own(be);
+        // first | inter | pitch | count | base | plane0[links] | elem (u32)
+        const uint64_t pitch = orz::plane_pitch(count), units = orz::plane_units(count);
+        std::vector<uint64_t> image(5 + (size_t)links + 1, 0);
+        image[1] = (uint64_t)(uintptr_t)d_inter;
+        image[2] = pitch;
+        image[3] = count;
+        image[4] = (uint64_t)(uintptr_t)d_base;
+        for (uint32_t k = 0; k < links; k++) image[5 + k] = (uint64_t)(uintptr_t)d_planes + (uint64_t)k * elem * pitch;
+        *(uint32_t*)(image.data() + 5 + links) = elem;
+        uint64_t* d = own.alloc<uint64_t>(image.size(), false);
+        be.h2d(d, image.data(), image.size() * 8);
+        const orz::PlaneTable t{d, d + 1, d + 5, d + 2, d + 3, (const uint32_t*)(d + 5 + links), 1};
+        ORZ_HIP_CHECK(hipEventCreate(&ev.a));
+        ORZ_HIP_CHECK(hipEventCreate(&ev.b));
+        for (int r = -1; r < reps; r++) {  // (the first launch warms up)
+            if (r == 0) ORZ_HIP_CHECK(hipEventRecord(ev.a, be.stream()));
+            be.launch((size_t)units, orz::PlaneMergeChain{t, d + 4, units, links});
+        }
+        ORZ_HIP_CHECK(hipEventRecord(ev.b, be.stream()));
+        ORZ_HIP_CHECK(hipEventSynchronize(ev.b));
+        float total = 0;
+        ORZ_HIP_CHECK(hipEventElapsedTime(&total, ev.a, ev.b));
+        *ms = (double)total / reps;
+        return ORZ_OK;
+    } catch (const std::exception& e) {
+        return fail(ORZ_ENODEV, e.what());
+    }
+}
 namespace {
 int plane_move_time(int device, void* d_inter, const void* d_base, void* d_planes, size_t count, uint32_t elem, int merge, int reps, double* ms);
 }
